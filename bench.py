@@ -22,6 +22,9 @@ labelled figures -- the headline and the BASELINE records always include the G2 
 
 `python bench.py --only aggregate --curve bls12 --n 65536 --in-flight 1` etc. run a single record (profiling runs;
 `--prepared` for the prepared-key-set path).
+
+`--dump-outputs DIR` writes what the headline's last timed step returned to its caller (verdict, status word, partial Miller
+product) as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import ctypes
@@ -35,9 +38,6 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, shared with torch's own streams):
-# with the default, two of the four verification lanes land on one queue and serialise.  Must be set before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -363,7 +363,9 @@ class Lanes:
         def collect(k):
             check(lib.bgls_select_context(k), "select_context")
             v = check(lib.bgls_final_verify_collect(cid), "final_verify_collect")
-            return settle(k, v) if settle else v
+            v = settle(k, v) if settle else v
+            self.last = (k, v)            # the lane and verdict of the most recently collected step (--dump-outputs)
+            return v
 
         try:
             if not overlap:
@@ -383,12 +385,39 @@ class Lanes:
             check(lib.bgls_select_context(0), "select_context")
 
 
+def timed_outputs(lanes):
+    """What the last timed step handed back to its caller, as float arrays for --dump-outputs: the verdict, the status word
+    (*d_flags) and the partial Miller product (GT wire format, canonical bytes: bgls_miller_product_dev's d_partial_out).
+    Read after the timed region has been synchronised, so the copies are not timed."""
+    import numpy as np
+    k, verdict = lanes.last
+    ln = lanes.lanes[k]
+    return {"verdict": np.array([verdict], dtype=np.float64),
+            "status": ln["words"][0:1].cpu().numpy().astype(np.float64),
+            "gt_partial": ln["part"].cpu().numpy().astype(np.float32)}
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, 64 MB in all at most."""
+    import numpy as np
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError("output %s is %s, not float32 / float64" % (name, a.dtype))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError("dumped outputs are %d bytes, over the 64 MB limit" % total)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 PREPARED_FPMUL = {0: 88 * 40 + 64 * 72 // 24, 1: 69 * 40 + 64 * 72 // 24}    # per pair: lines x (2 Fp2 products on 6 lanes + 4 scalings) + squarings / 24
 
 
-def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, in_flight, throughput, label, with_h2d=True, prepared=False):
+def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, in_flight, throughput, label, with_h2d=True, prepared=False, dump=None):
     """VerifyAggregateSignature over an n_total-signer batch of which this rank holds inst['n_local'] signers (the first
-    n_local of `inst`).  Returns the record dict on rank 0 (None elsewhere)."""
+    n_local of `inst`).  Returns the record dict on rank 0 (None elsewhere).  `dump` (a dict) receives what the last timed
+    step returned to its caller (see timed_outputs)."""
     cid, fp = inst["cid"], inst["fp"]
     gtb = 12 * fp
     n = inst["n_local"]
@@ -537,6 +566,8 @@ def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, i
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
         regions.append(elapsed)
+    if dump is not None:
+        dump.update(timed_outputs(lanes))
     stages = {s: stage(lib, s) for s in ("dup_check", "h2c", "miller", "reduce", "final_exp")}
     h2d_elapsed = None
     if with_h2d and world == 1:
@@ -902,7 +933,7 @@ def bench_small(lib, dev, inst, n, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (verifications) in each timed region; ms_per_step = region / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3, help="timed regions of --steps steps each; value = the median region")
     ap.add_argument("--n", "--signers", dest="n", type=int, default=1 << 20, help="signers of the headline batch (whole job)")
@@ -915,7 +946,14 @@ def main():
     ap.add_argument("--prepared", action="store_true", help="with --only aggregate: verify against a prepared key set")
     ap.add_argument("--x60-mode", type=int, default=None, help="development: bgls_set_miller_shape(4, MODE) -- role / priority / block-form word of k_miller_x60")
     ap.add_argument("--key-set", action="store_true", help="with --only multisig: the keys are a resident key set (bgls_keys_upload) instead of wire bytes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (verdict, status word, partial Miller "
+                         "product) as DIR/<name>.npy; the inputs are seeded, so equal arguments give equal inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.only not in (None, "aggregate"):
+        ap.error("--dump-outputs applies to the aggregate-verification workload (no --only, or --only aggregate)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -953,13 +991,16 @@ def main():
         return
     if args.only == "small":
         inst = make_instance(lib, CURVE[args.curve], args.n, 0xB6150000)
-        print(json.dumps(bench_small(lib, dev, inst, args.n, max(args.steps, 20))), flush=True)
+        print(json.dumps(bench_small(lib, dev, inst, args.n, args.steps)), flush=True)
         return
 
     cid = CURVE[args.curve]
     inst = shard_instance(cid, args.n, 0xB6150000 + 1 + cid)
+    outputs = {} if args.dump_outputs is not None else None
     head = bench_aggregate(lib, dev, inst, args.n, rank, world, args.steps, args.warmup, args.reps, args.in_flight, tp, "headline",
-                           prepared=args.prepared and args.only == "aggregate")
+                           prepared=args.prepared and args.only == "aggregate", dump=outputs)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     records = {}
     if args.only is None and not args.no_records:
         other = 1 - cid

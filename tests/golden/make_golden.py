@@ -23,7 +23,8 @@ from oracle.pyref.pairing import Pairing
 from oracle.pyref import h2c, scheme
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/curves/testcases"
+# the reference project's curves/testcases directory (only h2c_kat.json needs it): set BGLS_REF_TESTCASES when regenerating
+REF = os.environ.get("BGLS_REF_TESTCASES", "curves/testcases")
 
 
 def kat():

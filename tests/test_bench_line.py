@@ -8,7 +8,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench():
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     sys.path.insert(0, ROOT)
     import bench
     return bench
@@ -87,6 +86,22 @@ def test_line_shrinks_rather_than_overflowing():
     assert len(line) < 4096 and json.loads(line)["value"] > 0
     full["records"] = {"r%d" % i: _canned_record(bench, "bls12", 10) for i in range(40)}
     assert len(bench.compact_line(full)) < 4096
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, and nothing over 64 MB in all."""
+    import numpy as np
+    import pytest
+    bench = _bench()
+    arrays = {"verdict": np.array([1.0]), "gt_partial": np.arange(384, dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    for k, v in arrays.items():
+        got = np.load(str(tmp_path / "d" / (k + ".npy")))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "e"), {"raw": np.zeros(4, dtype=np.uint8)})
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "f"), {"big": np.zeros((64 << 20) // 8 + 1, dtype=np.float64)})
 
 
 def test_stage_time_is_per_call_not_per_scope():

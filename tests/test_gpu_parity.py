@@ -531,6 +531,30 @@ def test_bench_two_ranks_share_one_gpu():
     assert ms["n_gpus"] == 2 and ms["value"] > 0 and ms["scaling"] == "strong"
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the last timed step's verdict, status word and partial Miller product land as float .npy files,
+    and two runs with the same seeded inputs but different launch shapes (one vs four verifications in flight) dump the same arrays."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for in_flight in (1, 4):
+        d = tmp_path / ("inflight%d" % in_flight)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--only", "aggregate", "--signers", "4096", "--steps", "3",
+                              "--warmup", "1", "--reps", "1", "--in-flight", str(in_flight), "--no-cpu-baseline", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, (out.stdout[-800:], out.stderr[-1500:])
+        rec = json.loads(out.stdout.rstrip().splitlines()[-1])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert set(a) == {"verdict", "status", "gt_partial"}
+    assert a["verdict"].tolist() == [1.0] and a["status"].tolist() == [0.0]
+    assert a["gt_partial"].dtype == np.float32 and a["gt_partial"].shape == (12 * 32,) and a["gt_partial"].any()
+    for k in a:
+        assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+
+
 def test_two_contexts_in_flight(gpu_lib, curve):
     """bgls_select_context + bgls_final_verify_submit_dev / _collect: two verifications enqueued back to back on two
     contexts (own streams, own workspaces) give their own verdicts -- a valid instance and one with a flipped message bit."""

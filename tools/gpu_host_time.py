@@ -1,6 +1,5 @@
 import ctypes, os, sys, time, random
-sys.path.insert(0, "/root/repo")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from bgls_amd import _lib
 import bench

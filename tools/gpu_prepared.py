@@ -2,7 +2,6 @@
 """Development: time bgls_verify_aggregate_h on a prepared vs an unprepared key set.  usage: gpu_prepared.py [curve] [n]"""
 import ctypes, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import torch
 from bgls_amd import _lib
 import bench
