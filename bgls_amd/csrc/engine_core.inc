@@ -520,9 +520,10 @@ struct Engine {
     void *pa, *pb;
     Fp2<C>* red = nullptr;
     bool epilogue = cofactor;
-    if (npairs <= LAT_MAX && miller_shape() == 0) {
+    if ((npairs <= LAT_MAX && miller_shape() == 0) || npairs == 0) {
       // a handful of pairings: one block per pairing (k_miller_latx), the signature pair as one more block -- or, with uncleared
-      // BLS12-381 hash points, in the epilogue that raises the other pairs' product to the cofactor
+      // BLS12-381 hash points, in the epilogue that raises the other pairs' product to the cofactor.  The signature pair alone
+      // (npairs = 0) comes here under every shape: the throughput kernels need at least one pairing
       const bool sig_block = sig && !cofactor;
       const size_t blocks = npairs + (sig_block ? 1 : 0);
       if ((rc = c.get(WS_F_A, (blocks + 1) * 6 * sizeof(Fp2<C>), &pa))) return rc;
