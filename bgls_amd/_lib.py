@@ -28,6 +28,8 @@ SIGNATURES = {
     "bgls_g2_size": (sz, [ci]),
     "bgls_gt_size": (sz, [ci]),
     "bgls_verify_aggregate": (ci, [ci, u8p, u8p, u8p, u64p, sz, ci]),
+    "bgls_verify_aggregate_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci, u8p, u8p]),
+    "bgls_verify_aggregate_batch_dev": (ci, [ci, vp, vp, u64p, sz, vp, sz, sz, ci, u8p, u8p, vp]),
     "bgls_verify_multi": (ci, [ci, u8p, u8p, sz, u8p, sz]),
     "bgls_verify_multi_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci]),
     "bgls_aggregate_sets": (ci, [ci, ci, u8p, u64p, sz, u8p]),

@@ -103,6 +103,45 @@ def KoskVerifyAggregateSignature(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:
     return _verify_agg(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs], True)
 
 
+def _verify_agg_batch(curve, aggsigs, keys_per_instance, msgs_per_instance, allow_duplicates):
+    """One bgls_verify_aggregate_batch call for every instance made of Points of this curve; an instance that is not (mismatched lengths,
+    a foreign point, a KeySet) gets what _verify_agg says about it alone.  A call that fails as a whole (an encoding or hashing error
+    somewhere in the batch) is settled instance by instance, so that the list equals the single calls' results."""
+    if not (len(aggsigs) == len(keys_per_instance) == len(msgs_per_instance)):
+        raise ValueError("aggsigs, keys_per_instance and msgs_per_instance differ in length")
+    out = [False] * len(aggsigs)
+    batch = []
+    for b, (sig, keys, msgs) in enumerate(zip(aggsigs, keys_per_instance, msgs_per_instance)):
+        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet) and len(keys) == len(msgs)
+                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
+            batch.append(b)
+        else:
+            out[b] = _verify_agg(curve, sig, keys, msgs, allow_duplicates)
+    if not batch:
+        return out
+    inst_off = (ctypes.c_uint64 * (len(batch) + 1))()
+    for i, b in enumerate(batch):
+        inst_off[i + 1] = inst_off[i] + len(keys_per_instance[b])
+    msgs = [bytes(m) for b in batch for m in msgs_per_instance[b]]
+    verdicts = (ctypes.c_uint8 * len(batch))()
+    rc = _lib.load().bgls_verify_aggregate_batch(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
+                                                 _lib.buf(b"".join(k.raw for b in batch for k in keys_per_instance[b])), inst_off, len(batch),
+                                                 _lib.buf(b"".join(msgs)), _offsets(msgs), 1 if allow_duplicates else 0, verdicts, None)
+    for i, b in enumerate(batch):
+        out[b] = verdicts[i] == 1 if rc >= 0 else _verify_agg(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b], allow_duplicates)
+    return out
+
+
+def VerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
+    """len(aggsigs) independent VerifyAggregateSignature calls (bgls/bgls.go:82-84) in one batch: a list of bools, one per instance."""
+    return _verify_agg_batch(curve, aggsigs, keys_per_instance, msgs_per_instance, False)
+
+
+def KoskVerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
+    """The batch of KoskVerifyAggregateSignature calls (bgls/blsKosk.go:100-106): 0x01 prepended to every message, duplicates allowed."""
+    return _verify_agg_batch(curve, aggsigs, keys_per_instance, [[b"\x01" + bytes(m) for m in ms] for ms in msgs_per_instance], True)
+
+
 def _verify_multi(curve, aggsig, keys, msg):                  # bgls/bgls.go:89-92
     if isinstance(keys, KeySet):
         if keys.curve is not curve or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):

@@ -28,6 +28,37 @@ int bgls_verify_aggregate(int curve, const uint8_t* sig, const uint8_t* keys, co
   DISPATCH(curve, verify_aggregate_t<CV>(sig, keys, msg_blob, msg_off, n, allow_duplicates));
 } BGLS_ABI_GUARD
 
+// offsets of a batch of instances: monotone from 0, below 2^30 pairs in all
+static int inst_off_ok(const uint64_t* inst_off, size_t n_inst) {
+  if (inst_off[0] != 0) return fail(BGLS_ERR_ARG, "inst_off must start at 0");
+  for (size_t b = 0; b < n_inst; ++b)
+    if (inst_off[b + 1] < inst_off[b]) return fail(BGLS_ERR_ARG, "inst_off not monotone");
+  if (inst_off[n_inst] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  return 0;
+}
+
+int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* msg_blob,
+                                const uint64_t* msg_off, int allow_duplicates, uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = inst_off_ok(inst_off, n_inst))) return rc;
+  if (n_inst == 0) return 0;
+  if (!sigs || !verdicts || !msg_off || (inst_off[n_inst] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_aggregate_batch_t<CV>(sigs, keys, inst_off, n_inst, msg_blob, msg_off, allow_duplicates, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs,
+                                    size_t msg_len, size_t msg_stride, int allow_duplicates, uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
+  if (n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = inst_off_ok(inst_off, n_inst))) return rc;
+  if (n_inst == 0) return 0;
+  if (!d_sigs || !verdicts || (inst_off[n_inst] && (!d_keys || (msg_len && !d_msgs)))) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_aggregate_batch_dev_t<CV>(d_sigs, d_keys, inst_off, n_inst, d_msgs, msg_len, msg_stride, allow_duplicates, verdicts, gt_out, stream));
+} BGLS_ABI_GUARD
+
 int bgls_verify_multi(int curve, const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) try {
   if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
   if (!sig || (n && !keys) || (msg_len && !msg)) return fail(BGLS_ERR_ARG, "NULL argument");
@@ -304,7 +335,7 @@ int bgls_profile_enable(int on) try {
     Ctx& c = all[k];
     std::lock_guard<std::mutex> lk(c.mu);
     c.prof = on != 0;
-    for (int i = 0; i < 8; ++i) { c.stage_ms[i] = 0; c.stage_cnt[i] = 0; }
+    for (int i = 0; i < ST_NUM; ++i) { c.stage_ms[i] = 0; c.stage_cnt[i] = 0; }
   }
   return 0;
 } BGLS_ABI_GUARD

@@ -61,7 +61,8 @@ constexpr size_t MAX_BATCH = (size_t)1 << 30;
 constexpr size_t LAT_MAX = 128;
 
 // workspace slots
-enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T, WS_NUM };
+enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
+       WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_NUM };
 
 struct Ctx {
   std::mutex mu;
@@ -79,8 +80,9 @@ struct Ctx {
   struct Pending { hipEvent_t a, b; int stage; };
   std::vector<Pending> pending;
   std::vector<hipEvent_t> ev_pool;
-  double stage_ms[8] = {0};
-  unsigned long long stage_cnt[8] = {0};
+  double stage_ms[16] = {0};
+  unsigned long long stage_cnt[16] = {0};
+  std::vector<uint64_t> stage_tab;           // host tables of a batch verification (offsets, reduce passes) on their way to WS_BATCH_IDX
   hipEvent_t ev() {
     if (!ev_pool.empty()) { hipEvent_t e = ev_pool.back(); ev_pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -255,8 +257,10 @@ constexpr int miller_dbg() { return 0; }
 #endif
 
 // ST_SUM is opened ONCE per key sum (main pass + tree + conversion); ST_SUM_MAIN brackets the main-pass kernel alone, inside it
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_NUM };
-const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main"};
+// ST_SCATTER and ST_EPI are opened by the batch of independent verifications only (Engine::miller_product_batch): the padded layout
+// of its pairs and its batched epilogue
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_NUM };
+const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -280,7 +284,8 @@ Roctx& roctx() {
   static Roctx r;
   return r;
 }
-const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main"};
+const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
+                                          "bgls:scatter", "bgls:epilogue"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -415,6 +420,131 @@ struct Engine {
     Fp2<C>* red = nullptr;
     if ((rc = reduce(c, st, (Fp2<C>*)pa, (Fp2<C>*)pb, groups, &red))) return rc;
     return emit_partial(c, st, red, raw || sig != nullptr, sig, gl, d_partial);
+  }
+
+  // A batch of n_inst independent aggregate verifications (bgls_verify_aggregate_batch): instance b is the signature d_sigs[b]
+  // (wire bytes) and the pairs inst_off[b] .. inst_off[b + 1] of the flat keys / messages (inst_off: n_inst + 1 HOST offsets from 0, monotone).
+  // Every stage runs once for the whole batch: one duplicate scan (a duplicate within instance b sets d_iflags[b]), one hashing pass
+  // over all messages, a scatter of the pairs to padded positions (each instance a run of whole six-pairing groups), one k_miller_x60
+  // launch sequence in its 60-pairing form (the 64-form's last four pairings join groups 0..3 of their block, so a group could straddle
+  // two instances), a segmented reduce to one partial per instance, the batched epilogue (rest^h and the signature pair).  Writes
+  // n_inst GT partials (bytes, no final exponentiation) to d_partials; d_iflags: n_inst words, zeroed by the caller.
+  static int miller_product_batch(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
+                                  int check_dups, uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags) {
+    const size_t n = inst_off[n_inst];
+    if (n >= MAX_BATCH || n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    constexpr bool raw = C::CURVE_ID == 1;                // BLS12-381: uncleared hash points, the cofactor applied per instance in the epilogue
+    // host tables, uploaded in one copy: inst_off, pad_off, then the segment tables of the reduce passes ({start, count} words)
+    std::vector<uint64_t>& tab = c.stage_tab;
+    tab.assign(2 * (n_inst + 1), 0);
+    for (size_t b = 0; b <= n_inst; ++b) tab[b] = inst_off[b];
+    for (size_t b = 0; b < n_inst; ++b) tab[n_inst + 2 + b] = tab[n_inst + 1 + b] + (inst_off[b + 1] - inst_off[b] + 5) / 6 * 6;
+    const size_t n_pad = tab[2 * n_inst + 1];
+    if (n_pad >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    const size_t nb = (n_pad + 59) / 60, groups = nb * 10;
+    // reduce passes, planned on the host: segment b holds cnt[b] partials from pos[b]; a pass leaves ceil(cnt / R) of them (one for an
+    // empty segment), until every instance has exactly one.  Kernel per pass as in Engine::reduce: k_reduce_fx (R = 10) once at most
+    // REDUCE_FX_MAX partials are left, k_reduce_coop (R = REDUCE_R) above.
+    struct Pass { size_t at, nout; bool fx; int R; };
+    std::vector<Pass> passes;
+    std::vector<size_t> pos(n_inst), cnt(n_inst);
+    size_t total = 0, max_out = 1;
+    bool done = true;
+    for (size_t b = 0; b < n_inst; ++b) {
+      pos[b] = tab[n_inst + 1 + b] / 6;
+      cnt[b] = (tab[n_inst + 2 + b] - tab[n_inst + 1 + b]) / 6;
+      total += cnt[b];
+      done = done && cnt[b] == 1;
+    }
+    while (!done) {
+      const bool fx = !legacy(LG_REDUCE) && total <= REDUCE_FX_MAX;
+      const int R = fx ? 10 : REDUCE_R;
+      const size_t at = tab.size();
+      size_t nout = 0;
+      done = true;
+      for (size_t b = 0; b < n_inst; ++b) {
+        const size_t k = cnt[b] == 0 ? 1 : (cnt[b] + R - 1) / R;
+        for (size_t j = 0; j < k; ++j) {
+          const size_t lo = pos[b] + j * R, m = cnt[b] - j * R < (size_t)R ? cnt[b] - j * R : (size_t)R;
+          tab.push_back((uint64_t)(cnt[b] ? lo : 0) | ((uint64_t)(cnt[b] ? m : 0) << 32));
+        }
+        pos[b] = nout;
+        cnt[b] = k;
+        nout += k;
+        done = done && k == 1;
+      }
+      passes.push_back({at, nout, fx, R});
+      total = nout;
+      if (nout > max_out) max_out = nout;
+    }
+    void *d_tab, *g1s, *g1p, *keyp, *sigs, *epi;
+    int rc;
+    if ((rc = c.get(WS_BATCH_IDX, tab.size() * 8, &d_tab))) return rc;
+    if ((rc = c.get(WS_G1S, (n + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n_inst + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
+    if ((rc = c.get(WS_BATCH_EPI, (n_inst + 1) * 12 * sizeof(Fp2<C>), &epi))) return rc;
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
+    const uint64_t* d_inst_off = (const uint64_t*)d_tab;
+    const uint64_t* d_pad_off = d_inst_off + n_inst + 1;
+    if (check_dups && n >= 2) {
+      size_t cap = 1;
+      while (cap < 2 * n) cap <<= 1;
+      void* table;
+      if ((rc = c.get(WS_TABLE, cap * 4, &table))) return rc;
+      Scope sc(c, st, ST_DUP);
+      HIPCHK(hipMemsetAsync(table, 0, cap * 4, st));
+      kl::dup_check_seg(st, mv, n, d_inst_off, (uint32_t)n_inst, (uint32_t*)table, (uint32_t)(cap - 1), d_iflags, dup_seed());
+      HIPCHK(hipGetLastError());
+    }
+    if (n) {
+      Scope sc(c, st, ST_H2C);
+      if ((rc = hash_to_g1(c, st, mv, n, (Aff<G1F>*)g1s, d_flags, raw))) return rc;
+    }
+    kl::g1_parse<C>(st, d_sigs, n_inst, 1, (Aff<G1F>*)sigs, d_flags);                         // -sigma_b
+    void *pa, *pb;
+    if ((rc = c.get(WS_F_A, (groups + max_out + 1) * 6 * sizeof(Fp2<C>), &pa))) return rc;
+    if ((rc = c.get(WS_F_B, (max_out + 1) * 6 * sizeof(Fp2<C>), &pb))) return rc;
+    if (n_pad) {
+      if ((rc = c.get(WS_BATCH_G1, n_pad * sizeof(Aff<G1F>), &g1p))) return rc;
+      if ((rc = c.get(WS_BATCH_KEYS, n_pad * G2B, &keyp))) return rc;
+      {
+        Scope sc(c, st, ST_SCATTER);
+        kl::batch_scatter<C>(st, (const Aff<G1F>*)g1s, d_keys, d_inst_off, d_pad_off, n_inst, n_pad, (Aff<G1F>*)g1p, (uint8_t*)keyp);
+        HIPCHK(hipGetLastError());
+      }
+      constexpr size_t RES = 1024, XB = 32768;            // resident blocks, blocks per launch (as in Engine::miller)
+      const int xmode = g_x60_rot.load() >= 0 ? (g_x60_rot.load() & 15) : ((nb <= RES && !throughput_mode()) ? 8 : 0);
+      void* park;
+      if ((rc = c.get(WS_QP, kl::miller_x_park_bytes<C, 60>(nb < XB ? nb : XB), &park))) return rc;
+      Scope sc(c, st, ST_MILLER);
+      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
+        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
+        const size_t p0 = blk0 * 60;
+        kl::miller_x<C, 60>(st, (unsigned)nblocks, (const Aff<G1F>*)g1p + p0, (const uint8_t*)keyp + p0 * G2B, n_pad - p0, (Fp2<C>*)pa + blk0 * 60, d_flags,
+                            (uint32_t*)park, xmode);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    Fp2<C>* red = (Fp2<C>*)pa;
+    {
+      Scope sc(c, st, ST_REDUCE);
+      Fp2<C>* a = (Fp2<C>*)pa;
+      Fp2<C>* b = (Fp2<C>*)pb;
+      for (const Pass& p : passes) {
+        const uint32_t* seg = (const uint32_t*)(d_inst_off + p.at);
+        if (p.fx) kl::reduce_fx_seg<C>(st, a, seg, p.nout, b);
+        else kl::reduce_coop_seg<C>(st, a, seg, p.nout, p.R, b);
+        std::swap(a, b);
+      }
+      HIPCHK(hipGetLastError());
+      red = a;
+    }
+    const LineCoeffs<C>* gl = nullptr;
+    if ((rc = gen_lines(c, &gl))) return rc;
+    Scope sc(c, st, ST_EPI);
+    kl::epiloguex_seg<C>(st, n_inst, red, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
 
   // H(m_i) as affine Montgomery points.  raw (BLS12-381 only): points before cofactor clearing, for the cofactor-in-GT

@@ -50,6 +50,91 @@ int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* b
   return E::finalize(c, st, (const uint8_t*)d_part, 1, 1, (const uint32_t*)d_flags, nullptr);
 }
 
+// n_inst independent VerifyAggregateSignature calls (bgls/bgls.go:94-119) in one set of launches (Engine::miller_product_batch), then one
+// final exponentiation per instance in ONE launch; verdicts[b] = 1 / 0, returns the number of accepted instances.  An encoding or hashing
+// failure anywhere fails the whole call with the single call's code.
+template <class C>
+int verify_aggregate_batch_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
+                               int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+  // words: n_inst per-instance duplicate flags, n_inst verdicts, the call's flag word
+  void *d_res, *d_part;
+  int rc;
+  if ((rc = c.get(WS_BATCH_RES, (2 * n_inst + 1) * 4, &d_res))) return rc;
+  if ((rc = c.get(WS_PART, n_inst * E::GTB * (gt_out ? 2 : 1), &d_part))) return rc;
+  uint32_t* d_iflags = (uint32_t*)d_res;
+  uint32_t* d_verdicts = d_iflags + n_inst;
+  uint32_t* d_flags = d_verdicts + n_inst;
+  uint8_t* d_gt = gt_out ? (uint8_t*)d_part + n_inst * E::GTB : nullptr;
+  // an error return below leaves launches and the copy of the host tables (Ctx::stage_tab) in flight: drain the stream first
+  struct Drain {
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(st);
+    }
+  } drain{st};
+  HIPCHK(hipMemsetAsync(d_res, 0, (2 * n_inst + 1) * 4, st));
+  if ((rc = E::miller_product_batch(c, st, d_sigs, d_keys, mv, inst_off, n_inst, !allow_dups, (uint8_t*)d_part, d_iflags, d_flags))) return rc;
+  {
+    Scope sc(c, st, ST_FINAL);
+    kl::finalx_batch<C>(st, (const uint8_t*)d_part, n_inst, d_gt, d_verdicts, d_iflags, d_flags);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> words(n_inst + 1);
+  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n_inst + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n_inst * E::GTB, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  c.collect();
+  if ((rc = flags_to_rc(words[n_inst]))) return rc;
+  int accepted = 0;
+  for (size_t b = 0; b < n_inst; ++b) {
+    verdicts[b] = words[b] ? 1 : 0;
+    accepted += words[b] ? 1 : 0;
+  }
+  return accepted;
+}
+
+template <class C>
+int verify_aggregate_batch_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* blob, const uint64_t* off,
+                             int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = c.stream;
+  const size_t n = inst_off[n_inst];
+  for (size_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
+  const size_t blob_len = n ? off[n] : 0;
+  void *d_sigs, *d_keys, *d_blob, *d_off;
+  if ((rc = c.get(WS_IN_A, n_inst * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
+  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
+  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
+  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_inst * E::G1B, hipMemcpyHostToDevice, st));
+  if (n) HIPCHK(hipMemcpyAsync(d_keys, keys, n * E::G2B, hipMemcpyHostToDevice, st));
+  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
+  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
+}
+
+template <class C>
+int verify_aggregate_batch_dev_t(const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs, size_t msg_len,
+                                 size_t msg_stride, int allow_dups, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
+}
+
 template <class C>
 int verify_multi_dev_t(Ctx& c, hipStream_t st, const uint8_t* d_sig, const uint8_t* d_keys, size_t n, const uint8_t* d_msg,
                        size_t msg_len, bool submit_only = false, int key_src = 0) {

@@ -57,7 +57,51 @@ __global__ void __launch_bounds__(256) k_finalx(const uint8_t* partials, size_t 
   }
 }
 
+// bgls_verify_aggregate_batch: one block per instance, each the k_finalx block of ONE serialised partial with the final exponentiation.
+// Block b reads partials + b GTB and writes gt_out + b GTB (gt_out may be nullptr) and verdicts[b] = (result == 1 and inst_flags[b] clear:
+// no duplicate message within the instance); a non-canonical partial is OR-ed into *flags as FLAG_ENC.
+template <class C>
+__global__ void __launch_bounds__(256) k_finalx_batch(const uint8_t* partials, uint8_t* gt_out, uint32_t* verdicts, const uint32_t* inst_flags,
+                                                     uint32_t* flags) {
+  typedef FX<C> E;
+  const int lane = threadIdx.x;
+  const size_t b = blockIdx.x;
+  const int order_pos[6] = {5, 2, 4, 1, 3, 0};
+  bool bad = false;
+  if (lane < 6) {
+    const uint8_t* p = partials + b * 12 * C::FP_BYTES + (size_t)(2 * order_pos[lane]) * C::FP_BYTES;
+    const Fp<C> im = fp_from_be<C>(p), re = fp_from_be<C>(p + C::FP_BYTES);
+    if (fp_geq_p<C>(im) || fp_geq_p<C>(re)) bad = true;
+    fx_put<C>(FE_F, lane, X2<C, SX_T>{sx_from_plain<C>(re), sx_from_plain<C>(im)});
+  }
+  __syncthreads();
+  fx_final_exp<C>();
+  bool is_one = true;
+  if (lane < 6) {
+    const X2<C, SX_T> x = fx_ld2<C>(E::coef(FE_F, lane, 0));
+    const Fp2<C> v = {sx_to_mont<C>(x.c0), sx_to_mont<C>(x.c1)};
+    is_one = lane == 0 ? f2_eq<C>(v, f2_one<C>()) : f2_is_zero<C>(v);
+    if (gt_out) {
+      uint8_t* o = gt_out + b * 12 * C::FP_BYTES + (size_t)(2 * order_pos[lane]) * C::FP_BYTES;
+      fp_to_be<C>(o, fp_from_mont<C>(v.c1));
+      fp_to_be<C>(o + C::FP_BYTES, fp_from_mont<C>(v.c0));
+    }
+  }
+  const unsigned long long ball = __ballot(is_one);
+  const unsigned long long bball = __ballot(bad);
+  if (lane == 0) {
+    verdicts[b] = (ball == ~0ull && inst_flags[b] == 0u) ? 1u : 0u;
+    if (bball) atomicOr(flags, FLAG_ENC);
+  }
+}
+
 namespace kl {
+template <class C>
+void finalx_batch(hipStream_t st, const uint8_t* partials, size_t n_inst, uint8_t* gt_out, uint32_t* verdicts, const uint32_t* inst_flags, uint32_t* flags) {
+  k_finalx_batch<C><<<(unsigned)n_inst, 256, FX<C>::LDS_BYTES_PAIR, st>>>(partials, gt_out, verdicts, inst_flags, flags);
+}
+template void finalx_batch<BN254>(hipStream_t, const uint8_t*, size_t, uint8_t*, uint32_t*, const uint32_t*, uint32_t*);
+template void finalx_batch<BLS381>(hipStream_t, const uint8_t*, size_t, uint8_t*, uint32_t*, const uint32_t*, uint32_t*);
 template <class C>
 void finalx(hipStream_t st, const uint8_t* partials, size_t count, int do_final_exp, uint8_t* gt_out, uint32_t* verdict, uint32_t* flags) {
   k_finalx<C><<<1, 256, FX<C>::LDS_BYTES_PAIR, st>>>(partials, count, do_final_exp, gt_out, verdict, flags, nullptr, 0);

@@ -65,6 +65,48 @@ __global__ void k_dup_check(MsgView mv, size_t n, uint32_t* table, uint32_t mask
   atomicOr(flags, FLAG_DUP);          // bucketed scan: too long a run of taken slots -- undecided, reported as a hit (see above)
 }
 
+// The scan of a batch of independent instances (bgls_verify_aggregate_batch): records inst_off[b] .. inst_off[b + 1] are instance b
+// (inst_off: n_inst + 1 offsets on the device, from 0).  A duplicate counts WITHIN an instance only: the instance index is mixed into
+// the record's hash, a probe hit compares it before the bytes, and a hit sets inst_flags[b] instead of the call's flag word.  Exact scan
+// (table of at least 2 n slots, probes without a bound).
+__device__ __forceinline__ uint32_t inst_of(const uint64_t* inst_off, uint32_t n_inst, size_t i) {
+  uint32_t lo = 0, hi = n_inst;                             // inst_off[lo] <= i < inst_off[hi]
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (inst_off[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+__global__ void k_dup_check_seg(MsgView mv, size_t n, const uint64_t* inst_off, uint32_t n_inst, uint32_t* table, uint32_t mask, uint32_t* inst_flags,
+                                uint64_t seed) {
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t b = inst_of(inst_off, n_inst, i);
+  const uint8_t* m = mv.ptr(i);
+  const size_t len = mv.size(i);
+  uint32_t slot = (uint32_t)msg_hash64(m, len, seed ^ (0x9e3779b97f4a7c15ull * (b + 1ull))) & mask;
+  for (;;) {
+    uint32_t prev = atomicCAS(&table[slot], 0u, (uint32_t)i + 1u);
+    if (prev == 0u) return;
+    size_t j = prev - 1u;
+    if (inst_of(inst_off, n_inst, j) == b && mv.size(j) == len) {
+      const uint8_t* o = mv.ptr(j);
+      bool same = true;
+      for (size_t k = 0; k < len; ++k)
+        if (o[k] != m[k]) {
+          same = false;
+          break;
+        }
+      if (same) {
+        atomicOr(&inst_flags[b], FLAG_DUP);
+        return;
+      }
+    }
+    slot = (slot + 1u) & mask;
+  }
+}
+
 // alt-bn128 try-and-increment as compacting rounds (curves/hash.go:53-77 has data-dependent trip
 // counts: geometric(1/2) per message, so a per-lane loop idles most of the wave).  Round r tests
 // LPM consecutive counters of every still-unfinished message on LPM adjacent lanes; the LOWEST
@@ -433,6 +475,10 @@ __global__ void k_msg_digest(MsgView mv, size_t n, uint8_t* out) {
 namespace bgls {
 namespace kl {
 
+void dup_check_seg(hipStream_t st, MsgView mv, size_t n, const uint64_t* inst_off, uint32_t n_inst, uint32_t* table, uint32_t mask, uint32_t* inst_flags,
+                   uint64_t seed) {
+  k_dup_check_seg<<<nblk(n, 256), 256, 0, st>>>(mv, n, inst_off, n_inst, table, mask, inst_flags, seed);
+}
 void msg_digest(hipStream_t st, MsgView mv, size_t n, uint8_t* out) { k_msg_digest<<<nblk(n, 256), 256, 0, st>>>(mv, n, out); }
 
 // ---- the digest exchange of a multi-GPU verification as an all-to-all by bucket (round 6).  Rank r owns the digests whose first byte is r mod N.

@@ -436,7 +436,100 @@ __global__ void __launch_bounds__(128) k_reduce_fx(const Fp2<C>* in, size_t coun
   }
 }
 
+// ---- batched aggregate verification (bgls_verify_aggregate_batch): the same tails with one segment / one instance per block
+// Segmented k_reduce_fx: out[G] = prod in[seg[2G] .. seg[2G] + seg[2G + 1]), 0 .. 12 operands; an empty segment gives one (the partial
+// of an instance without keys).  seg: the host's per-pass table (engine_core.inc Engine::reduce_seg).
+template <class C>
+__global__ void __launch_bounds__(128) k_reduce_fx_seg(const Fp2<C>* in, const uint32_t* seg, Fp2<C>* out) {
+  typedef FX<C> E;
+  const int tid = threadIdx.x;
+  const size_t G = blockIdx.x, lo = seg[2 * G];
+  const int nin = (int)seg[2 * G + 1];
+  if (nin == 0) {
+    if (tid < 6) out[G * 6 + tid] = tid == 0 ? f2_one<C>() : f2_zero<C>();
+    return;
+  }
+  for (int idx = tid; idx < 6 * nin; idx += 128) {
+    const int part = idx / 6, coeff = idx % 6;
+    const Fp2<C> v = in[(lo + part) * 6 + coeff];
+    fx_put<C>(part, coeff, X2<C, SX_T>{sx_from_mont<C>(v.c0), sx_from_mont<C>(v.c1)});
+  }
+  __syncthreads();
+  for (int k = 1; k < nin; ++k) fx_mul<C>(0, 0, k);
+  if (tid < 6) {
+    const X2<C, SX_T> x = fx_ld2<C>(E::coef(0, tid, 0));
+    out[G * 6 + tid] = Fp2<C>{sx_to_mont<C>(x.c0), sx_to_mont<C>(x.c1)};
+  }
+}
+
+// k_epilogue_ax over a batch: blocks 2b and 2b + 1 are instance b's two chains -- the signature pair (-sigma_b, g2) on the generator's
+// lines into tmp[12 b ..], and rest_b^h (rest: one reduced partial per instance) into tmp[12 b + 6 ..] -- as the two blocks of the
+// single form with first_role 0.
+template <class C>
+__global__ void __launch_bounds__(256) k_epilogue_ax_seg(const Fp2<C>* rest, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp,
+                                                         uint32_t* flags) {
+  typedef FX<C> E;
+  const size_t b = blockIdx.x >> 1;
+  if ((blockIdx.x & 1) == 0) {
+    if (threadIdx.x >= 64 * 3) return;                      // the Miller block is three waves
+    miller_latx_block<C, 2>(sigs + b, nullptr, 0, 0, gen_lines, tmp + b * 12, flags, 0);
+    return;
+  }
+  const int lane = threadIdx.x;
+  enum { S_BASE = 0, S_ACC = 1, S_SQ = 2 };
+  if (lane < 6) {
+    const Fp2<C> v = rest[b * 6 + lane];
+    fx_put<C>(S_BASE, lane, X2<C, SX_T>{sx_from_mont<C>(v.c0), sx_from_mont<C>(v.c1)});
+  }
+  __syncthreads();
+  int res = S_BASE;
+  if constexpr (C::CURVE_ID == 1) {
+    fx_pow<C>(S_ACC, S_BASE, C::COFACTOR, C::COFACTOR_BITS, S_SQ);
+    res = S_ACC;
+  }
+  if (lane < 6) {
+    const X2<C, SX_T> x = fx_ld2<C>(E::coef(res, lane, 0));
+    tmp[b * 12 + 6 + lane] = Fp2<C>{sx_to_mont<C>(x.c0), sx_to_mont<C>(x.c1)};
+  }
+}
+// k_epilogue_bx over a batch: block b multiplies instance b's two chains and writes its GT bytes to out + b * 12 FP_BYTES
+template <class C>
+__global__ void __launch_bounds__(64) k_epilogue_bx_seg(const Fp2<C>* tmp, uint8_t* out) {
+  typedef FX<C> E;
+  const int lane = threadIdx.x;
+  const size_t b = blockIdx.x;
+  if (lane < 6) {
+    const Fp2<C> x = tmp[b * 12 + lane], y = tmp[b * 12 + 6 + lane];
+    fx_put<C>(0, lane, X2<C, SX_T>{sx_from_mont<C>(x.c0), sx_from_mont<C>(x.c1)});
+    fx_put<C>(1, lane, X2<C, SX_T>{sx_from_mont<C>(y.c0), sx_from_mont<C>(y.c1)});
+  }
+  wave_sync();
+  fx_mul1<C>(0, 0, 1);
+  if (lane < 6) {
+    const int order_pos[6] = {5, 2, 4, 1, 3, 0};
+    const X2<C, SX_T> x = fx_ld2<C>(E::coef(0, lane, 0));
+    uint8_t* o = out + b * 12 * C::FP_BYTES + (size_t)(2 * order_pos[lane]) * C::FP_BYTES;
+    fp_to_be<C>(o, fp_from_mont<C>(sx_to_mont<C>(x.c1)));
+    fp_to_be<C>(o + C::FP_BYTES, fp_from_mont<C>(sx_to_mont<C>(x.c0)));
+  }
+}
+
 namespace kl {
+template <class C>
+void reduce_fx_seg(hipStream_t st, const Fp2<C>* in, const uint32_t* seg, size_t nout, Fp2<C>* out) {
+  k_reduce_fx_seg<C><<<(unsigned)nout, 128, FX<C>::LDS_BYTES, st>>>(in, seg, out);
+}
+template <class C>
+void epiloguex_seg(hipStream_t st, size_t n_inst, const Fp2<C>* rest, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out,
+                   uint32_t* flags) {
+  k_epilogue_ax_seg<C><<<(unsigned)(2 * n_inst), 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sigs, gen_lines, tmp, flags);
+  k_epilogue_bx_seg<C><<<(unsigned)n_inst, 64, FX<C>::LDS_BYTES, st>>>(tmp, out);
+}
+template void reduce_fx_seg<BN254>(hipStream_t, const Fp2<BN254>*, const uint32_t*, size_t, Fp2<BN254>*);
+template void reduce_fx_seg<BLS381>(hipStream_t, const Fp2<BLS381>*, const uint32_t*, size_t, Fp2<BLS381>*);
+template void epiloguex_seg<BN254>(hipStream_t, size_t, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*, uint32_t*);
+template void epiloguex_seg<BLS381>(hipStream_t, size_t, const Fp2<BLS381>*, const Aff<F1<BLS381>>*, const LineCoeffs<BLS381>*, Fp2<BLS381>*, uint8_t*,
+                                    uint32_t*);
 template <class C>
 void reduce_fx(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* out) {
   const size_t nout = (count + R - 1) / R;

@@ -57,6 +57,27 @@ __global__ void __launch_bounds__(64) k_reduce_coop(const Fp2<C>* in, size_t cou
   }
   if (live && has) out[G * 6 + j] = acc;
 }
+// segmented form (bgls_verify_aggregate_batch): out[G] = prod in[seg[2G] .. seg[2G] + seg[2G + 1]) for G < nout, 0 .. R operands; an empty
+// segment gives one.  seg: the host's per-pass table (engine_core.inc Engine::reduce_seg).
+template <class C>
+__global__ void __launch_bounds__(64) k_reduce_coop_seg(const Fp2<C>* in, const uint32_t* seg, size_t nout, int R, Fp2<C>* out) {
+  typedef Coop<C> K;
+  CoopLane<C> ln;
+  const int j = ln.j, gb = ln.gb;
+  const bool live = ln.live;
+  const size_t G = (size_t)blockIdx.x * K::GROUPS + ln.g;
+  const bool has = G < nout;
+  const size_t lo = has ? seg[2 * G] : 0;
+  const int cnt = has ? (int)seg[2 * G + 1] : 0;
+  Fp2<C> acc = cnt > 0 ? in[lo * 6 + j] : (j == 0 ? f2_one<C>() : f2_zero<C>());
+#pragma unroll 1
+  for (int t = 1; t < R; ++t) {                           // uniform trip count; missing operands are 1
+    coop_publish<C>(gb + K::RB, j, acc, live);
+    Fp2<C> x = t < cnt ? in[(lo + t) * 6 + j] : (j == 0 ? f2_one<C>() : f2_zero<C>());
+    acc = coop_mul<C>(gb, j, x, live);
+  }
+  if (live && has) out[G * 6 + j] = acc;
+}
 
 template <class C>
 __global__ void k_w_to_bytes(const Fp2<C>* in, uint8_t* out) {
@@ -491,6 +512,10 @@ void reduce_coop(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* 
   k_reduce_coop<C><<<nblk(nout, Coop<C>::GROUPS), 64, Coop<C>::WAVE_BYTES, st>>>(in, count, R, out);
 }
 template <class C>
+void reduce_coop_seg(hipStream_t st, const Fp2<C>* in, const uint32_t* seg, size_t nout, int R, Fp2<C>* out) {
+  k_reduce_coop_seg<C><<<nblk(nout, Coop<C>::GROUPS), 64, Coop<C>::WAVE_BYTES, st>>>(in, seg, nout, R, out);
+}
+template <class C>
 void w_to_bytes(hipStream_t st, const Fp2<C>* in, uint8_t* out) {
   k_w_to_bytes<C><<<1, 64, 0, st>>>(in, out);
 }
@@ -518,6 +543,7 @@ void gt_pow(hipStream_t st, const uint8_t* gt_in, const uint8_t* k_be32, int neg
 #define BGLS_INST(C)                                                                                               \
   template void gen_lines<C>(hipStream_t, LineCoeffs<C>*, int*);                                                   \
   template void reduce_coop<C>(hipStream_t, const Fp2<C>*, size_t, int, Fp2<C>*);                                  \
+  template void reduce_coop_seg<C>(hipStream_t, const Fp2<C>*, const uint32_t*, size_t, int, Fp2<C>*);            \
   template void w_to_bytes<C>(hipStream_t, const Fp2<C>*, uint8_t*);                                               \
   template void gt_pow<C>(hipStream_t, const uint8_t*, const uint8_t*, int, uint8_t*, uint32_t*);
 BGLS_INST(BGLS_TAIL_CURVE)

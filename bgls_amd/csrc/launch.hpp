@@ -12,6 +12,9 @@ void digest_pack(hipStream_t st, const uint8_t* dig, size_t n, uint8_t* out, siz
 constexpr uint32_t DUP_MAX_PROBE = 1023;      // bucketed duplicate scan: probes per record before it reports "undecided"
 void dup_check(hipStream_t st, MsgView mv, size_t n, uint32_t* table, uint32_t mask, uint32_t* flags, uint32_t bucket = 0, uint32_t n_buckets = 1, uint64_t seed = 0,
                bool unbounded = false);
+// segmented scan of a batch of instances (inst_off: n_inst + 1 device offsets): a duplicate within instance b sets inst_flags[b]
+void dup_check_seg(hipStream_t st, MsgView mv, size_t n, const uint64_t* inst_off, uint32_t n_inst, uint32_t* table, uint32_t mask, uint32_t* inst_flags,
+                   uint64_t seed);
 void msg_digest(hipStream_t st, MsgView mv, size_t n, uint8_t* out);
 void h2c_bn(hipStream_t st, MsgView mv, size_t n, uint32_t* lists, uint32_t* counters, Aff<F1<BN254>>* out, uint32_t* flags, bool lean);
 void h2c_bls(hipStream_t st, MsgView mv, size_t n, Jac<F1<BLS381>>* pts, uint32_t* kinds, Aff<F1<BLS381>>* out, bool raw);   // pts: 2n Jacobian work items
@@ -78,6 +81,10 @@ template <class C, int NP>
 void miller_x(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, Fp2<C>* out, uint32_t* flags, uint32_t* park, int rot_mode);
 template <class C, int NP> size_t miller_x_park_bytes(size_t nblocks);
 
+// ---- k_batchagg.hip: hash points and keys of a batch of instances to their padded positions (one instance per run of whole six-pairing groups)
+template <class C>
+void batch_scatter(hipStream_t st, const Aff<F1<C>>* g1s, const uint8_t* keys, const uint64_t* inst_off, const uint64_t* pad_off, size_t n_inst, size_t n_pad,
+                   Aff<F1<C>>* g1_out, uint8_t* key_out);
 
 // prepared key sets (prepared.hpp): bytes per key of the line table, per pairing of the point table, per key of k_prepare's scratch
 struct PrepSizes { size_t line_bytes_per_key, point_bytes, tmp_bytes_per_key; };
@@ -91,6 +98,7 @@ template <class C> void fold_prep(hipStream_t st, const uint32_t* table, const u
 // ---- k_tail_bn.hip / k_tail_bls.hip
 template <class C> void gen_lines(hipStream_t st, LineCoeffs<C>* table, int* nsteps);
 template <class C> void reduce_coop(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* out);
+template <class C> void reduce_coop_seg(hipStream_t st, const Fp2<C>* in, const uint32_t* seg, size_t nout, int R, Fp2<C>* out);
 template <class C> void w_to_bytes(hipStream_t st, const Fp2<C>* in, uint8_t* out);
 template <class C> void final36(hipStream_t st, const uint8_t* partials, size_t count, int do_final_exp, uint8_t* gt_out, uint32_t* verdict, uint32_t* flags);
 template <class C> void finalx(hipStream_t st, const uint8_t* partials, size_t count, int do_final_exp, uint8_t* gt_out, uint32_t* verdict, uint32_t* flags);

@@ -520,6 +520,55 @@ func HipVerifyBatchMulti(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, 
 	return C.bgls_verify_multi_batch(c.id, p(sb), p(kb), &koff[0], C.size_t(len(msgs)), p(blob), &moff[0], 1) == 1
 }
 
+// HipVerifyAggregateBatch is len(aggsigs) independent VerifyAggregateSignature calls (bgls/bgls.go:82-84) in one
+// bgls_verify_aggregate_batch call: ok[b] is instance b's verdict.  Instance b is aggsigs[b] against pubkeys[b] and msgs[b]
+// (prefix the Kosk 0x01 and pass allowDuplicates = true for KoskVerifyAggregateSignature).  An instance that is not made of this
+// curve's points gets false; a call that fails as a whole (an encoding or hashing error somewhere in the batch) is settled by the
+// single calls, so that ok equals their results.  Uncompiled text, as the rest of this file.
+func HipVerifyAggregateBatch(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, msgs [][][]byte, allowDuplicates bool) []bool {
+	ok := make([]bool, len(aggsigs))
+	c, isHip := curve.(*hipCurve)
+	if !isHip || len(aggsigs) != len(pubkeys) || len(pubkeys) != len(msgs) {
+		return ok
+	}
+	dup := C.int(0)
+	if allowDuplicates {
+		dup = 1
+	}
+	var sb, kb, blob []byte
+	var batch []int
+	ioff := []C.uint64_t{0}
+	moff := []C.uint64_t{0}
+	for b := range aggsigs {
+		s, isHipPoint := aggsigs[b].(*hipPoint)
+		one, ok3 := hipKeyBytes(c, pubkeys[b])
+		if !isHipPoint || s.group != C.BGLS_G1 || !ok3 || len(pubkeys[b]) != len(msgs[b]) {
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		kb = append(kb, one...)
+		ioff = append(ioff, ioff[len(ioff)-1]+C.uint64_t(len(pubkeys[b])))
+		for _, m := range msgs[b] {
+			blob = append(blob, m...)
+			moff = append(moff, C.uint64_t(len(blob)))
+		}
+	}
+	if len(batch) == 0 {
+		return ok
+	}
+	verdicts := make([]byte, len(batch))
+	rc := C.bgls_verify_aggregate_batch(c.id, p(sb), p(kb), &ioff[0], C.size_t(len(batch)), p(blob), &moff[0], dup, p(verdicts), nil)
+	for i, b := range batch {
+		if rc >= 0 {
+			ok[b] = verdicts[i] == 1
+		} else {
+			ok[b] = HipVerifyAggregate(curve, aggsigs[b], pubkeys[b], msgs[b], allowDuplicates)
+		}
+	}
+	return ok
+}
+
 // HipUnmarshalG2Batch decodes n compressed or uncompressed alt-bn128 keys in one call (the batch form of UnmarshalG2 for
 // key sets arriving over the wire); ok[i] mirrors the per-point (Point, bool).
 func HipUnmarshalG2Batch(curve CurveSystem, data []byte, n int) ([]Point, []bool) {

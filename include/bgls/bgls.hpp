@@ -168,6 +168,58 @@ inline bool VerifyMultiSignatureWithHAE(const CurveSystem* curve, const Point& a
   if (aggsig.curve != curve || aggsig.group != BGLS_G1 || !detail::g2_bytes(curve, pubkeys, kb)) return false;
   return bgls_verify_multi_hae(curve->id, aggsig.raw.data(), kb.data(), pubkeys.size(), msg.data(), msg.size()) == 1;
 }
+// B independent verifyAggSig calls in ONE bgls_verify_aggregate_batch call: one bool per instance.  An instance that is not made of this
+// curve's points (or whose lengths differ) gets verifyAggSig's answer alone; a call that fails as a whole (an encoding or hashing error
+// somewhere in the batch) is settled instance by instance, so that the list equals the single calls' results.
+inline std::vector<bool> verifyAggSigs(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                       const std::vector<std::vector<Bytes>>& msgs, bool allowDuplicates) {
+  std::vector<bool> out(aggsigs.size(), false);
+  if (keys.size() != aggsigs.size() || msgs.size() != aggsigs.size()) return out;
+  std::vector<size_t> batch;
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> ioff(1, 0), moff(1, 0);
+  for (size_t b = 0; b < aggsigs.size(); ++b) {
+    Bytes one;
+    if (aggsigs[b].curve != curve || aggsigs[b].group != BGLS_G1 || keys[b].size() != msgs[b].size() || !detail::g2_bytes(curve, keys[b], one)) {
+      out[b] = verifyAggSig(curve, aggsigs[b], keys[b], msgs[b], allowDuplicates);
+      continue;
+    }
+    batch.push_back(b);
+    sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+    kb.insert(kb.end(), one.begin(), one.end());
+    ioff.push_back(ioff.back() + keys[b].size());
+    for (const Bytes& m : msgs[b]) {
+      blob.insert(blob.end(), m.begin(), m.end());
+      moff.push_back(blob.size());
+    }
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = bgls_verify_aggregate_batch(curve->id, sb.data(), kb.data(), ioff.data(), batch.size(), blob.data(), moff.data(), allowDuplicates ? 1 : 0,
+                                             verdicts.data(), nullptr);
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const size_t b = batch[i];
+    out[b] = rc >= 0 ? verdicts[i] == 1 : verifyAggSig(curve, aggsigs[b], keys[b], msgs[b], allowDuplicates);
+  }
+  return out;
+}
+// B independent VerifyAggregateSignature calls (bgls/bgls.go:82-84) in one batch
+inline std::vector<bool> VerifyAggregateSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                   const std::vector<std::vector<Bytes>>& msgs) {
+  return verifyAggSigs(curve, aggsigs, keys, msgs, false);
+}
+// B independent KoskVerifyAggregateSignature calls (bgls/blsKosk.go:100-106): 0x01 prepended to every message, duplicates allowed
+inline std::vector<bool> KoskVerifyAggregateSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs,
+                                                       const std::vector<std::vector<Point>>& keys, const std::vector<std::vector<Bytes>>& msgs) {
+  std::vector<std::vector<Bytes>> pm(msgs.size());
+  for (size_t b = 0; b < msgs.size(); ++b)
+    for (const Bytes& m : msgs[b]) {
+      Bytes one(1, 1);
+      one.insert(one.end(), m.begin(), m.end());
+      pm[b].push_back(one);
+    }
+  return verifyAggSigs(curve, aggsigs, keys, pm, true);
+}
 // KoskVerifyBatchMultiSignature, bgls/blsKosk.go:126-133: one call -- every key set summed in one launch, ONE aggregate verification
 inline bool KoskVerifyBatchMultiSignature(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& pubkeys,
                                           const std::vector<Bytes>& msgs) {

@@ -83,6 +83,22 @@ size_t bgls_gt_size(int curve); /* 384 / 576 */
 int bgls_verify_aggregate(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob,
                           const uint64_t* msg_off, size_t n, int allow_duplicates);
 
+/* n_inst independent VerifyAggregateSignature calls (bgls/bgls.go:82-84,94-119) in one set of launches.  Instance b is the
+ * signature sigs[b] (n_inst G1 points), the keys keys[inst_off[b] .. inst_off[b+1]) and the messages with the same indices
+ * (msg_off: inst_off[n_inst] + 1 entries, as in bgls_verify_aggregate).  inst_off: n_inst + 1 offsets, monotone from 0, below
+ * 2^30 pairs in all (BGLS_ERR_ARG otherwise); n_inst == 0 returns 0.
+ * Verdicts: verdicts[b] = 1 / 0 is what bgls_verify_aggregate returns for instance b alone -- an instance without keys is accepted
+ * iff its signature is the point at infinity.  With allow_duplicates = 0 duplicate messages are searched for WITHIN each instance
+ * (such an instance gets 0); the same message in two instances is no duplicate.  gt_out: NULL or n_inst GT elements, gt_out[b] =
+ * e(-sig_b, g2) * prod e(H(m_i), pk_i) after the final exponentiation, byte-equal to what the single path computes for instance b.
+ * Errors: a non-canonical or off-curve key or signature, a degenerate point step or an exhausted hash ANYWHERE in the batch fails
+ * the whole call with the single call's code (BGLS_ERR_ENCODING / BGLS_ERR_HASH) and leaves verdicts undefined -- the Verify*
+ * convention that keys are constructed Points (see above); bgls_check_points is the per-item validation.
+ * Returns the number of accepted instances (>= 0) or < 0. */
+int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst,
+                                const uint8_t* msg_blob, const uint64_t* msg_off, int allow_duplicates, uint8_t* verdicts,
+                                uint8_t* gt_out);
+
 /* verifyMultiSignature (bgls/bgls.go:89-92): apk = sum(keys) (AggregatePoints,
  * curves/curve.go:73-121) then VerifySingleSignature (bgls/bgls.go:59-70) on msg.
  * KoskVerifyMultiSignature (bgls/blsKosk.go:117-120) is this call with 0x01 prepended to msg. */
@@ -309,6 +325,13 @@ int bgls_verify_multi_batch_dev(int curve, const void* d_sigs, const void* d_key
                                 const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream);
 int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
                                        const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream);
+/* bgls_verify_aggregate_batch with signatures, keys and messages on the device: d_sigs = n_inst G1 points, d_keys = inst_off[n_inst]
+ * G2 points, message i at d_msgs + i * msg_stride (msg_len bytes).  inst_off stays a HOST array (it plans the launches).  Same
+ * semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns.  Every batch runs the Miller
+ * stage as k_miller_x60 in its 60-pairing form, whatever bgls_set_miller_shape says. */
+int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst,
+                                    const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates,
+                                    uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* verify_multi with keys already on the device. */
 int bgls_verify_multi_dev(int curve, const void* d_sig, const void* d_keys, size_t n, const void* d_msg,
                           size_t msg_len, void* stream);
