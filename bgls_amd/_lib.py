@@ -32,6 +32,8 @@ SIGNATURES = {
     "bgls_verify_aggregate_batch_dev": (ci, [ci, vp, vp, u64p, sz, vp, sz, sz, ci, u8p, u8p, vp]),
     "bgls_verify_multi": (ci, [ci, u8p, u8p, sz, u8p, sz]),
     "bgls_verify_multi_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci]),
+    "bgls_verify_multi_sets": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p]),
+    "bgls_verify_multi_sets_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, vp]),
     "bgls_aggregate_sets": (ci, [ci, ci, u8p, u64p, sz, u8p]),
     "bgls_verify_multi_batch_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, ci, vp]),
     "bgls_verify_multi_batch_submit_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, ci, vp]),

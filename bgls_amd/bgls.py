@@ -169,6 +169,56 @@ def KoskVerifyMultiSignature(curve, aggsig, keys, msg):       # bgls/blsKosk.go:
     return _verify_multi(curve, aggsig, keys, b"\x01" + bytes(msg))
 
 
+def _verify_multi_sets(curve, aggsigs, keys_per_set, msgs):
+    """One bgls_verify_multi_sets call for every set made of Points of this curve; a set that is not (a nil or foreign signature, a
+    foreign key, a KeySet) gets what _verify_multi says about it alone.  A call that fails as a whole (an encoding or hashing error
+    somewhere in the batch) is settled set by set, so that the list equals the single calls' results."""
+    if not (len(aggsigs) == len(keys_per_set) == len(msgs)):
+        raise ValueError("aggsigs, keys_per_set and msgs differ in length")
+    out = [False] * len(aggsigs)
+    batch = []
+    for b, (sig, keys) in enumerate(zip(aggsigs, keys_per_set)):
+        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet)
+                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
+            batch.append(b)
+        else:
+            out[b] = _verify_multi(curve, sig, keys, bytes(msgs[b]))
+    if not batch:
+        return out
+    key_off = (ctypes.c_uint64 * (len(batch) + 1))()
+    for i, b in enumerate(batch):
+        key_off[i + 1] = key_off[i] + len(keys_per_set[b])
+    ms = [bytes(msgs[b]) for b in batch]
+    verdicts = (ctypes.c_uint8 * len(batch))()
+    rc = _lib.load().bgls_verify_multi_sets(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
+                                            _lib.buf(b"".join(k.raw for b in batch for k in keys_per_set[b])), key_off, len(batch),
+                                            _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None)
+    for i, b in enumerate(batch):
+        out[b] = verdicts[i] == 1 if rc >= 0 else _verify_multi(curve, aggsigs[b], keys_per_set[b], ms[i])
+    return out
+
+
+def VerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
+    """len(aggsigs) independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one batch: a list of bools, one per set."""
+    return _verify_multi_sets(curve, aggsigs, pubkeys, msgs)
+
+
+def KoskVerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
+    """len(aggsigs) independent KoskVerifyMultiSignature calls (bgls/blsKosk.go:117-120) in one batch: 0x01 prepended to every message,
+    a list of bools, one per set (pubkeys[b]: the signers of msgs[b])."""
+    return _verify_multi_sets(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
+
+
+def VerifySingleSignatures(curve, sigs, pubkeys, msgs):
+    """len(sigs) independent VerifySingleSignature calls (bgls/bgls.go:59-70) in one batch: one key per set, a list of bools."""
+    return _verify_multi_sets(curve, sigs, [[pk] for pk in pubkeys], msgs)
+
+
+def KoskVerifySingleSignatures(curve, sigs, pubkeys, msgs):
+    """The batch of KoskVerifySingleSignature calls (bgls/blsKosk.go:86-90): 0x01 prepended to every message."""
+    return VerifySingleSignatures(curve, sigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
+
+
 def KoskVerifyBatchMultiSignature(curve, aggsigs, pubkeys, msgs):      # bgls/blsKosk.go:126-133
     """aggsigs: one multi-signature per message, pubkeys[i]: the signers of message i.  One call: the key sums of all sets
     in one launch, then ONE aggregate verification over len(msgs) pairs (the reference: AggregateSignatures, len(msgs) x

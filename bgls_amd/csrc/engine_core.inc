@@ -547,6 +547,51 @@ struct Engine {
     return 0;
   }
 
+  // A batch of n_sets independent multi-signature verifications (bgls_verify_multi_sets): set b is the signature d_sigs[b] (wire
+  // bytes), the key sum d_apks[b] (wire bytes, Engine::sum_sets) and message b of mv.  Every stage runs once for the batch: one
+  // hashing pass, the parse of the -sigma_b, one k_miller_sets launch sequence (one accumulator per set: the hash pair and, on
+  // alt-bn128, the signature pair on the generator lines), on BLS12-381 the batched epilogue (rest^h, then the signature pair: the
+  // single path's order for uncleared hash points).  Writes n_sets GT partials (bytes, no final exponentiation) to d_partials.
+  static int miller_multi_sets(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_apks, MsgView mv, size_t n_sets, uint8_t* d_partials,
+                               uint32_t* d_flags) {
+    if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    constexpr bool bls = C::CURVE_ID == 1;                // uncleared hash points, the cofactor applied per set in the epilogue
+    void *g1s, *sigs, *park, *rest = nullptr, *epi = nullptr;
+    int rc;
+    constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
+    const size_t spb = kl::miller_sets_per_block<C>(), nb = (n_sets + spb - 1) / spb;
+    if ((rc = c.get(WS_G1S, (n_sets + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n_sets + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
+    if ((rc = c.get(WS_QP, kl::miller_sets_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
+    if (bls) {
+      if ((rc = c.get(WS_F_A, (n_sets + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
+      if ((rc = c.get(WS_BATCH_EPI, (n_sets + 1) * 12 * sizeof(Fp2<C>), &epi))) return rc;
+    }
+    const LineCoeffs<C>* gl = nullptr;
+    if ((rc = gen_lines(c, &gl))) return rc;
+    {
+      Scope sc(c, st, ST_H2C);
+      if ((rc = hash_to_g1(c, st, mv, n_sets, (Aff<G1F>*)g1s, d_flags, bls))) return rc;
+    }
+    kl::g1_parse<C>(st, d_sigs, n_sets, 1, (Aff<G1F>*)sigs, d_flags);                         // -sigma_b
+    {
+      Scope sc(c, st, ST_MILLER);
+      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
+        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
+        const size_t s0 = blk0 * spb;
+        kl::miller_sets<C>(st, (unsigned)nblocks, (const Aff<G1F>*)g1s + s0, d_apks + s0 * G2B, (const Aff<G1F>*)sigs + s0, gl, n_sets - s0,
+                           bls ? (Fp2<C>*)rest + s0 * 6 : nullptr, bls ? nullptr : d_partials + s0 * GTB, d_flags, (uint32_t*)park);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    if (bls) {
+      Scope sc(c, st, ST_EPI);
+      kl::epiloguex_seg<C>(st, n_sets, (const Fp2<C>*)rest, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
+
   // H(m_i) as affine Montgomery points.  raw (BLS12-381 only): points before cofactor clearing, for the cofactor-in-GT
   // verification path (DESIGN.md section 3).
   static int hash_to_g1(Ctx& c, hipStream_t st, MsgView mv, size_t n, Aff<G1F>* out, uint32_t* d_flags, bool raw = false) {

@@ -275,6 +275,110 @@ int aggregate_sets_t(int group, const uint8_t* pts, const uint64_t* set_off, siz
   return flags_to_rc(f);
 }
 
+// n_sets independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one set of launches: every key sum in one pass
+// (Engine::sum_sets), then Engine::miller_multi_sets and one final exponentiation per set in ONE launch; verdicts[b] = 1 / 0, returns the
+// number of accepted sets.  d_key_off: n_sets + 1 device offsets, already checked (monotone, no set above max_set).  An encoding or
+// hashing failure anywhere fails the whole call with the single call's code.
+template <class C>
+int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, const uint64_t* d_key_off, size_t n_sets, size_t max_set,
+                          MsgView mv, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+  // words: n_sets per-set flags (no duplicate rule: they stay zero), n_sets verdicts, the call's flag word
+  void *d_res, *d_part, *d_apks;
+  int rc;
+  if ((rc = c.get(WS_BATCH_RES, (2 * n_sets + 1) * 4, &d_res))) return rc;
+  if ((rc = c.get(WS_PART, n_sets * E::GTB * (gt_out ? 2 : 1), &d_part))) return rc;
+  if ((rc = c.get(WS_SEG_KEYS, (n_sets + 1) * E::G2B, &d_apks))) return rc;
+  uint32_t* d_iflags = (uint32_t*)d_res;
+  uint32_t* d_verdicts = d_iflags + n_sets;
+  uint32_t* d_flags = d_verdicts + n_sets;
+  uint8_t* d_gt = gt_out ? (uint8_t*)d_part + n_sets * E::GTB : nullptr;
+  struct Drain {                                          // an error return below leaves launches in flight: drain the stream first
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(st);
+    }
+  } drain{st};
+  HIPCHK(hipMemsetAsync(d_res, 0, (2 * n_sets + 1) * 4, st));
+  if ((rc = E::sum_sets(c, st, BGLS_G2, d_keys, d_key_off, n_sets, max_set, (uint8_t*)d_apks, d_flags))) return rc;   // apk_b = AggregateKeys(set b)
+  if ((rc = E::miller_multi_sets(c, st, d_sigs, (const uint8_t*)d_apks, mv, n_sets, (uint8_t*)d_part, d_flags))) return rc;
+  {
+    Scope sc(c, st, ST_FINAL);
+    kl::finalx_batch<C>(st, (const uint8_t*)d_part, n_sets, d_gt, d_verdicts, d_iflags, d_flags);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> words(n_sets + 1);
+  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n_sets + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n_sets * E::GTB, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  c.collect();
+  if ((rc = flags_to_rc(words[n_sets]))) return rc;
+  int accepted = 0;
+  for (size_t b = 0; b < n_sets; ++b) {
+    verdicts[b] = words[b] ? 1 : 0;
+    accepted += words[b] ? 1 : 0;
+  }
+  return accepted;
+}
+
+template <class C>
+int verify_multi_sets_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* blob, const uint64_t* off,
+                        uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = c.stream;
+  size_t max_set = 0;
+  for (size_t i = 0; i < n_sets; ++i)
+    if (key_off[i + 1] - key_off[i] > max_set) max_set = key_off[i + 1] - key_off[i];
+  const size_t k0 = key_off[0], nkeys = key_off[n_sets] - k0, blob_len = off[n_sets];
+  void *d_sigs, *d_keys, *d_blob, *d_off, *d_koff;
+  if ((rc = c.get(WS_IN_A, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.get(WS_IN_B, (nkeys + 1) * E::G2B, &d_keys))) return rc;
+  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
+  if ((rc = c.get(WS_IN_D, (n_sets + 1) * 8, &d_off))) return rc;
+  if ((rc = c.get(WS_SEG_OFF, (n_sets + 1) * 8, &d_koff))) return rc;
+  std::vector<uint64_t> rel(n_sets + 1);
+  for (size_t i = 0; i <= n_sets; ++i) rel[i] = key_off[i] - k0;
+  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_sets * E::G1B, hipMemcpyHostToDevice, st));
+  if (nkeys) HIPCHK(hipMemcpyAsync(d_keys, keys + k0 * E::G2B, nkeys * E::G2B, hipMemcpyHostToDevice, st));
+  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_off, off, (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_koff, rel.data(), (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));                       // rel goes out of scope
+  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  return verify_multi_sets_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets, max_set, mv, verdicts, gt_out);
+}
+
+template <class C>
+int verify_multi_sets_dev_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs, size_t msg_len,
+                            size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  // the offsets are the caller's device words: check them here (monotone from 0, no set above max_set, below 2^30 keys), so that no
+  // launch reads past the keys
+  std::vector<uint64_t> koff(n_sets + 1);
+  HIPCHK(hipMemcpyAsync(koff.data(), d_key_off, (n_sets + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (koff[0] != 0) return fail(BGLS_ERR_ARG, "key_off must start at 0");
+  for (size_t b = 0; b < n_sets; ++b) {
+    if (koff[b + 1] < koff[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
+    if (koff[b + 1] - koff[b] > max_set) return fail(BGLS_ERR_ARG, "a set is larger than max_set");
+  }
+  if (koff[n_sets] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (koff[n_sets] && !d_keys) return fail(BGLS_ERR_ARG, "NULL argument");
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_multi_sets_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
+}
+
 template <class C>
 int verify_multi_t(const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) {
   typedef Engine<C> E;

@@ -86,6 +86,15 @@ template <class C>
 void batch_scatter(hipStream_t st, const Aff<F1<C>>* g1s, const uint8_t* keys, const uint64_t* inst_off, const uint64_t* pad_off, size_t n_inst, size_t n_pad,
                    Aff<F1<C>>* g1_out, uint8_t* key_out);
 
+// ---- k_millersets.hip: the Miller loop of n two-pairing sets (bgls_verify_multi_sets), one accumulator per set, sets_per_block sets per block.
+// Set b: (g1s[b], key sum g2s[b]) and, on alt-bn128, (sigs[b], g2) on the generator lines -- GT bytes (no final exponentiation) to
+// out_bytes + b GTB; on BLS12-381 the hash pair alone, six w-basis Fp2 to out_w + 6 b (the epilogue's rest).  park: miller_sets_park_bytes.
+template <class C>
+void miller_sets(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1s, const uint8_t* g2s, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, size_t n,
+                 Fp2<C>* out_w, uint8_t* out_bytes, uint32_t* flags, uint32_t* park);
+template <class C> size_t miller_sets_park_bytes(size_t nblocks);
+template <class C> size_t miller_sets_per_block();
+
 // prepared key sets (prepared.hpp): bytes per key of the line table, per pairing of the point table, per key of k_prepare's scratch
 struct PrepSizes { size_t line_bytes_per_key, point_bytes, tmp_bytes_per_key; };
 template <class C> PrepSizes prep_sizes();

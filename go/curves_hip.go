@@ -569,6 +569,49 @@ func HipVerifyAggregateBatch(curve CurveSystem, aggsigs []Point, pubkeys [][]Poi
 	return ok
 }
 
+// HipVerifyMultiSets is len(aggsigs) independent bgls.verifyMultiSignature calls (bgls/bgls.go:89-92) in one bgls_verify_multi_sets
+// call: ok[b] is set b's verdict, set b being aggsigs[b] against pubkeys[b] on msgs[b] (prefix the Kosk 0x01 for KoskVerifyMultiSignature;
+// one key per set is VerifySingleSignature).  A set that is not made of this curve's points gets HipVerifyMulti's answer alone; a call
+// that fails as a whole is settled by the single calls, so that ok equals their results.  Uncompiled text, as the rest of this file.
+func HipVerifyMultiSets(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, msgs [][]byte) []bool {
+	ok := make([]bool, len(aggsigs))
+	c, isHip := curve.(*hipCurve)
+	if !isHip || len(aggsigs) != len(pubkeys) || len(pubkeys) != len(msgs) {
+		return ok
+	}
+	var sb, kb, blob []byte
+	var batch []int
+	koff := []C.uint64_t{0}
+	moff := []C.uint64_t{0}
+	for b := range aggsigs {
+		s, isHipPoint := aggsigs[b].(*hipPoint)
+		one, ok3 := hipKeyBytes(c, pubkeys[b])
+		if !isHipPoint || s.group != C.BGLS_G1 || !ok3 {
+			ok[b] = HipVerifyMulti(curve, aggsigs[b], pubkeys[b], msgs[b])
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		kb = append(kb, one...)
+		koff = append(koff, koff[len(koff)-1]+C.uint64_t(len(pubkeys[b])))
+		blob = append(blob, msgs[b]...)
+		moff = append(moff, C.uint64_t(len(blob)))
+	}
+	if len(batch) == 0 {
+		return ok
+	}
+	verdicts := make([]byte, len(batch))
+	rc := C.bgls_verify_multi_sets(c.id, p(sb), p(kb), &koff[0], C.size_t(len(batch)), p(blob), &moff[0], p(verdicts), nil)
+	for i, b := range batch {
+		if rc >= 0 {
+			ok[b] = verdicts[i] == 1
+		} else {
+			ok[b] = HipVerifyMulti(curve, aggsigs[b], pubkeys[b], msgs[b])
+		}
+	}
+	return ok
+}
+
 // HipUnmarshalG2Batch decodes n compressed or uncompressed alt-bn128 keys in one call (the batch form of UnmarshalG2 for
 // key sets arriving over the wire); ok[i] mirrors the per-point (Point, bool).
 func HipUnmarshalG2Batch(curve CurveSystem, data []byte, n int) ([]Point, []bool) {

@@ -220,6 +220,63 @@ inline std::vector<bool> KoskVerifyAggregateSignatures(const CurveSystem* curve,
     }
   return verifyAggSigs(curve, aggsigs, keys, pm, true);
 }
+// B independent verifyMultiSignature calls (bgls/bgls.go:89-92) in ONE bgls_verify_multi_sets call: one bool per set.  A set that is not
+// made of this curve's points gets verifyMultiSignature's answer alone; a call that fails as a whole (an encoding or hashing error
+// somewhere in the batch) is settled set by set, so that the list equals the single calls' results.
+inline std::vector<bool> verifyMultiSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                               const std::vector<Bytes>& msgs) {
+  std::vector<bool> out(aggsigs.size(), false);
+  if (keys.size() != aggsigs.size() || msgs.size() != aggsigs.size()) return out;
+  std::vector<size_t> batch;
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> koff(1, 0), moff(1, 0);
+  for (size_t b = 0; b < aggsigs.size(); ++b) {
+    Bytes one;
+    if (aggsigs[b].curve != curve || aggsigs[b].group != BGLS_G1 || !detail::g2_bytes(curve, keys[b], one)) {
+      out[b] = verifyMultiSignature(curve, aggsigs[b], keys[b], msgs[b]);
+      continue;
+    }
+    batch.push_back(b);
+    sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+    kb.insert(kb.end(), one.begin(), one.end());
+    koff.push_back(koff.back() + keys[b].size());
+    blob.insert(blob.end(), msgs[b].begin(), msgs[b].end());
+    moff.push_back(blob.size());
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = bgls_verify_multi_sets(curve->id, sb.data(), kb.data(), koff.data(), batch.size(), blob.data(), moff.data(), verdicts.data(), nullptr);
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const size_t b = batch[i];
+    out[b] = rc >= 0 ? verdicts[i] == 1 : verifyMultiSignature(curve, aggsigs[b], keys[b], msgs[b]);
+  }
+  return out;
+}
+// B independent KoskVerifyMultiSignature calls (bgls/blsKosk.go:117-120): 0x01 prepended to every message
+inline std::vector<bool> KoskVerifyMultiSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                   const std::vector<Bytes>& msgs) {
+  std::vector<Bytes> pm;
+  for (const Bytes& m : msgs) {
+    Bytes one(1, 1);
+    one.insert(one.end(), m.begin(), m.end());
+    pm.push_back(one);
+  }
+  return verifyMultiSignatures(curve, aggsigs, keys, pm);
+}
+// B independent VerifySingleSignature calls (bgls/bgls.go:59-70): one key per set
+inline std::vector<bool> VerifySingleSignatures(const CurveSystem* curve, const std::vector<Point>& sigs, const std::vector<Point>& pubKeys,
+                                                const std::vector<Bytes>& msgs) {
+  std::vector<std::vector<Point>> keys;
+  for (const Point& k : pubKeys) keys.push_back({k});
+  return verifyMultiSignatures(curve, sigs, keys, msgs);
+}
+// B independent KoskVerifySingleSignature calls (bgls/blsKosk.go:86-90)
+inline std::vector<bool> KoskVerifySingleSignatures(const CurveSystem* curve, const std::vector<Point>& sigs, const std::vector<Point>& pubKeys,
+                                                    const std::vector<Bytes>& msgs) {
+  std::vector<std::vector<Point>> keys;
+  for (const Point& k : pubKeys) keys.push_back({k});
+  return KoskVerifyMultiSignatures(curve, sigs, keys, msgs);
+}
 // KoskVerifyBatchMultiSignature, bgls/blsKosk.go:126-133: one call -- every key set summed in one launch, ONE aggregate verification
 inline bool KoskVerifyBatchMultiSignature(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& pubkeys,
                                           const std::vector<Bytes>& msgs) {

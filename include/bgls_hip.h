@@ -118,6 +118,19 @@ int bgls_verify_multi(int curve, const uint8_t* sig, const uint8_t* keys, size_t
  * the caller. */
 int bgls_verify_multi_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
                             const uint8_t* msg_blob, const uint64_t* msg_off, int allow_duplicates);
+/* n_sets independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one set of launches.  Set b is the signature sigs[b]
+ * (n_sets G1 points), the keys keys[key_off[b] .. key_off[b+1]) and the message msg_blob[msg_off[b] .. msg_off[b+1]).  A set of
+ * one key is VerifySingleSignature (bgls/bgls.go:59-70): this is also the batched single-signature check.
+ * Verdicts: verdicts[b] = 1 / 0 is exactly what bgls_verify_multi returns for set b alone -- an empty set sums to the point at
+ * infinity, as in the single call.  There is no duplicate rule (one message per set): the same message in several sets is fine.
+ * gt_out: NULL or n_sets GT elements, gt_out[b] = e(-sig_b, g2) * e(H(m_b), apk_b) after the final exponentiation, byte-equal to
+ * what the single path computes for set b.
+ * Errors as bgls_verify_aggregate_batch: a non-canonical or off-curve key or signature, a degenerate point step or an exhausted hash
+ * ANYWHERE fails the whole call with the single call's code and leaves verdicts undefined.  Size limits are bgls_verify_multi_batch's
+ * (BGLS_ERR_ARG past them); non-monotone key_off / msg_off are BGLS_ERR_ARG; n_sets == 0 returns 0.
+ * Returns the number of accepted sets (>= 0) or < 0. */
+int bgls_verify_multi_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
+                           const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out);
 /* AggregatePoints (curves/curve.go:73-121) over n_sets sets in one pass: out[b] = sum of pts[set_off[b] .. set_off[b+1])
  * (an empty set gives the point at infinity).  What the n_sets AggregateKeys calls of blsKosk.go:128-131 cost. */
 int bgls_aggregate_sets(int curve, int group, const uint8_t* pts, const uint64_t* set_off, size_t n_sets, uint8_t* out);
@@ -325,6 +338,13 @@ int bgls_verify_multi_batch_dev(int curve, const void* d_sigs, const void* d_key
                                 const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream);
 int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
                                        const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream);
+/* bgls_verify_multi_sets with everything on the device: d_key_off and max_set as in bgls_verify_multi_batch_dev (n_sets + 1
+ * uint64 offsets from 0, the largest set's size; the call reads them back and returns BGLS_ERR_ARG unless they are monotone and
+ * within max_set), message b at d_msgs + b * msg_stride (msg_len bytes).  Same semantics and return value; synchronises `stream`
+ * (NULL: the context's stream) before it returns.  The Miller stage is k_miller_sets whatever bgls_set_miller_shape says. */
+int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
+                               size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
+                               uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* bgls_verify_aggregate_batch with signatures, keys and messages on the device: d_sigs = n_inst G1 points, d_keys = inst_off[n_inst]
  * G2 points, message i at d_msgs + i * msg_stride (msg_len bytes).  inst_off stays a HOST array (it plans the launches).  Same
  * semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns.  Every batch runs the Miller
