@@ -112,6 +112,22 @@ int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys
   DISPATCH(curve, verify_multi_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, uint8_t* verdicts,
+                         uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n == 0) return 0;
+  if (!sigmas || !rs || !keys || !ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, bb_verify_t<CV>(sigmas, rs, keys, ms, n, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n, uint8_t* verdicts,
+                             uint8_t* gt_out, void* stream) try {
+  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n == 0) return 0;
+  if (!d_sigmas || !d_rs || !d_keys || !d_ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, bb_verify_dev_t<CV>(d_sigmas, d_rs, d_keys, d_ms, n, verdicts, gt_out, stream));
+} BGLS_ABI_GUARD
+
 int bgls_pairing_product(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) try {
   if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
   if (!gt_out || (n && (!g1s || !g2s))) return fail(BGLS_ERR_ARG, "NULL argument");

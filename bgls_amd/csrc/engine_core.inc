@@ -258,9 +258,9 @@ constexpr int miller_dbg() { return 0; }
 
 // ST_SUM is opened ONCE per key sum (main pass + tree + conversion); ST_SUM_MAIN brackets the main-pass kernel alone, inside it
 // ST_SCATTER and ST_EPI are opened by the batch of independent verifications only (Engine::miller_product_batch): the padded layout
-// of its pairs and its batched epilogue
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_NUM };
-const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue"};
+// of its pairs and its batched epilogue; ST_BB_KEYS by the batched Boneh-Boyen verification only (Engine::miller_bb: its Q_b = m_b g2 + U_b + r_b V_b)
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_NUM };
+const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -285,7 +285,7 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -312,6 +312,9 @@ inline uint64_t dup_seed() {
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27;
   return x;
 }
+
+// window multiples of a generator for this device (engine_verify.inc), built on first use
+template <class C> int fixed_base_table(Ctx& c, int group, const void** out);
 
 template <class C>
 struct Engine {
@@ -587,6 +590,54 @@ struct Engine {
     if (bls) {
       Scope sc(c, st, ST_EPI);
       kl::epiloguex_seg<C>(st, n_sets, (const Fp2<C>*)rest, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // A batch of n independent Boneh-Boyen verifications (bgls_bb_verify_batch): item b is sigma_b (d_sigmas, wire bytes) against
+  // Q_b = m_b g2 + U_b + r_b V_b (d_keys: U_b || V_b, d_rs / d_ms: 32-byte big-endian scalars).  Every stage runs once for the batch:
+  // the parse of the sigma_b, k_bb_keys (Q_b as wire bytes; item n is the reference pair (g1, g2)), one k_miller_sets launch sequence
+  // with sigma_b in the hash-point slot and Q_b in the key-sum slot (alt-bn128: no generator pair, every signature slot at infinity;
+  // BLS12-381: the w-basis value straight to bytes -- no cofactor power, sigma is a G1 point), writing n + 1 GT partials (bytes, no
+  // final exponentiation) to d_partials.
+  static int miller_bb(Ctx& c, hipStream_t st, const uint8_t* d_sigmas, const uint8_t* d_rs, const uint8_t* d_keys, const uint8_t* d_ms, size_t n,
+                       uint8_t* d_partials, uint32_t* d_flags) {
+    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    constexpr bool bls = C::CURVE_ID == 1;
+    const size_t m = n + 1;                               // the items and the reference pair
+    void *g1s, *qs, *nosig, *park, *rest = nullptr;
+    const void* fb;
+    int rc;
+    constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
+    const size_t spb = kl::miller_sets_per_block<C>(), nb = (m + spb - 1) / spb;
+    if ((rc = c.get(WS_G1S, (m + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+    if ((rc = c.get(WS_SEG_KEYS, (m + 1) * G2B, &qs))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (m + 1) * sizeof(Aff<G1F>), &nosig))) return rc;
+    if ((rc = c.get(WS_QP, kl::miller_sets_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
+    if (bls && (rc = c.get(WS_F_A, (m + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
+    const LineCoeffs<C>* gl = nullptr;
+    if ((rc = gen_lines(c, &gl))) return rc;
+    if ((rc = fixed_base_table<C>(c, BGLS_G2, &fb))) return rc;
+    kl::g1_parse<C>(st, d_sigmas, n, 0, (Aff<G1F>*)g1s, d_flags);
+    {
+      Scope sc(c, st, ST_BB_KEYS);
+      kl::bb_keys<C>(st, d_keys, d_rs, d_ms, fb, n, (uint8_t*)qs, (Aff<G1F>*)g1s, bls ? nullptr : (Aff<G1F>*)nosig, d_flags);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      Scope sc(c, st, ST_MILLER);
+      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
+        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
+        const size_t s0 = blk0 * spb;
+        kl::miller_sets<C>(st, (unsigned)nblocks, (const Aff<G1F>*)g1s + s0, (const uint8_t*)qs + s0 * G2B, (const Aff<G1F>*)nosig + s0, gl, m - s0,
+                           bls ? (Fp2<C>*)rest + s0 * 6 : nullptr, bls ? nullptr : d_partials + s0 * GTB, d_flags, (uint32_t*)park);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    if (bls) {
+      Scope sc(c, st, ST_EPI);
+      kl::bb_w_bytes<C>(st, (const Fp2<C>*)rest, m, d_partials);
       HIPCHK(hipGetLastError());
     }
     return 0;

@@ -379,6 +379,86 @@ int verify_multi_sets_dev_t(const void* d_sigs, const void* d_keys, const void* 
   return verify_multi_sets_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
 }
 
+// n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one set of launches: Engine::miller_bb (item n is the reference pair
+// (g1, g2)), one final exponentiation per item in ONE launch, then verdicts[b] = (e(sigma_b, Q_b) == e(g1, g2)) byte for byte on the
+// device; returns the number of accepted items.  gt_out (nullable): the n GT elements.  An encoding failure anywhere (sigma, U, V)
+// or a degenerate point step fails the whole call.
+template <class C>
+int bb_verify_run(Ctx& c, hipStream_t st, const uint8_t* d_sigmas, const uint8_t* d_rs, const uint8_t* d_keys, const uint8_t* d_ms, size_t n,
+                  uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+  const size_t m = n + 1;
+  // words: m per-item flags (always zero), m verdicts of the final exponentiation against one (unused), n verdicts, the call's flag word
+  void *d_res, *d_part;
+  int rc;
+  if ((rc = c.get(WS_BATCH_RES, (3 * m + 1) * 4, &d_res))) return rc;
+  if ((rc = c.get(WS_PART, 2 * m * E::GTB, &d_part))) return rc;
+  uint32_t* d_iflags = (uint32_t*)d_res;
+  uint32_t* d_fx = d_iflags + m;
+  uint32_t* d_verdicts = d_fx + m;
+  uint32_t* d_flags = d_verdicts + n;
+  uint8_t* d_gt = (uint8_t*)d_part + m * E::GTB;
+  struct Drain {                                          // an error return below leaves launches in flight: drain the stream first
+    hipStream_t st;
+    bool armed = true;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(st);
+    }
+  } drain{st};
+  HIPCHK(hipMemsetAsync(d_res, 0, (3 * m + 1) * 4, st));
+  if ((rc = E::miller_bb(c, st, d_sigmas, d_rs, d_keys, d_ms, n, (uint8_t*)d_part, d_flags))) return rc;
+  {
+    Scope sc(c, st, ST_FINAL);
+    kl::finalx_batch<C>(st, (const uint8_t*)d_part, m, d_gt, d_fx, d_iflags, d_flags);
+    kl::bb_verdicts<C>(st, d_gt, n, d_verdicts);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> words(n + 1);
+  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n * E::GTB, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  c.collect();
+  if ((rc = flags_to_rc(words[n]))) return rc;
+  int accepted = 0;
+  for (size_t b = 0; b < n; ++b) {
+    verdicts[b] = words[b] ? 1 : 0;
+    accepted += words[b] ? 1 : 0;
+  }
+  return accepted;
+}
+
+template <class C>
+int bb_verify_t(const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = c.stream;
+  void *d_sigmas, *d_rs, *d_keys, *d_ms;
+  if ((rc = c.get(WS_IN_A, n * E::G1B, &d_sigmas))) return rc;
+  if ((rc = c.get(WS_IN_B, n * 32, &d_rs))) return rc;
+  if ((rc = c.get(WS_IN_C, n * 2 * E::G2B, &d_keys))) return rc;
+  if ((rc = c.get(WS_IN_D, n * 32, &d_ms))) return rc;
+  HIPCHK(hipMemcpyAsync(d_sigmas, sigmas, n * E::G1B, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_rs, rs, n * 32, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_keys, keys, n * 2 * E::G2B, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_ms, ms, n * 32, hipMemcpyHostToDevice, st));
+  return bb_verify_run<C>(c, st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
+}
+
+template <class C>
+int bb_verify_dev_t(const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  return bb_verify_run<C>(c, st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
+}
+
 template <class C>
 int verify_multi_t(const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) {
   typedef Engine<C> E;

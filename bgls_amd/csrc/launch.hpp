@@ -95,6 +95,16 @@ void miller_sets(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1s, const 
 template <class C> size_t miller_sets_park_bytes(size_t nblocks);
 template <class C> size_t miller_sets_per_block();
 
+// ---- k_bbsigs.hip: batched Boneh-Boyen verification (bgls_bb_verify_batch).  bb_keys: Q_b = m_b g2 + U_b + r_b V_b as wire bytes to
+// q_out + b G2B for b < n (keys: n x (U || V) wire bytes, rs / ms: n x 32-byte big-endian scalars, fb_g2: the fixed-base table of g2), and
+// the reference pair (g1, g2) at index n: g1s[n], q_out + n G2B; nosig (nullable): n + 1 G1 points at infinity.  bb_w_bytes: n w-basis
+// Miller values (six Fp2 each) to GT bytes.  bb_verdicts: verdicts[b] = (gt[b] == gt[n]) for b < n.
+template <class C>
+void bb_keys(hipStream_t st, const uint8_t* keys, const uint8_t* rs, const uint8_t* ms, const void* fb_g2, size_t n, uint8_t* q_out, Aff<F1<C>>* g1s,
+             Aff<F1<C>>* nosig, uint32_t* flags);
+template <class C> void bb_w_bytes(hipStream_t st, const Fp2<C>* w, size_t n, uint8_t* out);
+template <class C> void bb_verdicts(hipStream_t st, const uint8_t* gt, size_t n, uint32_t* verdicts);
+
 // prepared key sets (prepared.hpp): bytes per key of the line table, per pairing of the point table, per key of k_prepare's scratch
 struct PrepSizes { size_t line_bytes_per_key, point_bytes, tmp_bytes_per_key; };
 template <class C> PrepSizes prep_sizes();

@@ -612,6 +612,55 @@ func HipVerifyMultiSets(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, m
 	return ok
 }
 
+// HipBBVerifyBatch is len(sigmas) independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one bgls_bb_verify_batch call: ok[b] is
+// item b's verdict, item b being the signature (sigmas[b], rs[b]) on the message scalar ms[b] under the key (us[b], vs[b]) (for
+// VerifyHashed pass blake2b256(msg) mod the order as ms[b]).  Negative scalars are reduced modulo the group order, as are magnitudes
+// of 2^256 or more; other values are used as given.  An item that is not made of this curve's points is rejected; a call that fails
+// as a whole (an encoding error somewhere) is settled item by item.  Uncompiled text, as the rest of this file.
+func HipBBVerifyBatch(curve CurveSystem, sigmas []Point, rs []*big.Int, us []Point, vs []Point, ms []*big.Int) []bool {
+	ok := make([]bool, len(sigmas))
+	c, isHip := curve.(*hipCurve)
+	if !isHip || len(rs) != len(sigmas) || len(us) != len(sigmas) || len(vs) != len(sigmas) || len(ms) != len(sigmas) {
+		return ok
+	}
+	mag := func(k *big.Int) []byte {
+		if k.Sign() < 0 {
+			k = new(big.Int).Mod(k, c.base.GetG1Order())
+		}
+		sc, _ := c.scalar32(k)
+		return sc
+	}
+	var sb, rb, kb, mb []byte
+	var batch []int
+	for b := range sigmas {
+		s, ok1 := sigmas[b].(*hipPoint)
+		u, ok2 := us[b].(*hipPoint)
+		v, ok3 := vs[b].(*hipPoint)
+		if !ok1 || !ok2 || !ok3 || s.group != C.BGLS_G1 || u.group != C.BGLS_G2 || v.group != C.BGLS_G2 || s.c != c || u.c != c || v.c != c {
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		rb = append(rb, mag(rs[b])...)
+		kb = append(kb, u.raw...)
+		kb = append(kb, v.raw...)
+		mb = append(mb, mag(ms[b])...)
+	}
+	if len(batch) == 0 {
+		return ok
+	}
+	verdicts := make([]byte, len(batch))
+	rc := C.bgls_bb_verify_batch(c.id, p(sb), p(rb), p(kb), p(mb), C.size_t(len(batch)), p(verdicts), nil)
+	for i, b := range batch {
+		if rc >= 0 {
+			ok[b] = verdicts[i] == 1
+		} else if len(batch) > 1 {
+			ok[b] = HipBBVerifyBatch(curve, sigmas[b:b+1], rs[b:b+1], us[b:b+1], vs[b:b+1], ms[b:b+1])[0]
+		}
+	}
+	return ok
+}
+
 // HipUnmarshalG2Batch decodes n compressed or uncompressed alt-bn128 keys in one call (the batch form of UnmarshalG2 for
 // key sets arriving over the wire); ok[i] mirrors the per-point (Point, bool).
 func HipUnmarshalG2Batch(curve CurveSystem, data []byte, n int) ([]Point, []bool) {

@@ -308,3 +308,41 @@ inline bool KoskVerifyMultiSignatureWithMultiplicity(const CurveSystem* curve, c
 }
 
 }  // namespace bgls_go
+
+// ---- Boneh-Boyen signatures (package bbsigs, bbsigs/bbsigs.go) ----
+// bgls::bb_verify_batch: n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in ONE bgls_bb_verify_batch call, one bool per
+// item.  Item b is the signature (sigmas[b], rs[b]) on the message scalar ms[b] under the key (us[b], vs[b]); scalars are 32-byte
+// big-endian magnitudes, used as given (reduce negative or larger big.Ints modulo the order first, as the Python mirror does).  An
+// item that is not made of this curve's points, or whose scalars are not 32 bytes, is rejected; a call that fails as a whole (an
+// encoding error somewhere in the batch) is settled item by item.  (A function in namespace bgls: the header's public name for the
+// call, next to the Go-named mirror bgls_go.)
+namespace bgls {
+inline std::vector<bool> bb_verify_batch(const curves::CurveSystem* curve, const std::vector<curves::Point>& sigmas, const std::vector<curves::Bytes>& rs,
+                                         const std::vector<curves::Point>& us, const std::vector<curves::Point>& vs, const std::vector<curves::Bytes>& ms) {
+  const size_t n = sigmas.size();
+  std::vector<bool> out(n, false);
+  if (rs.size() != n || us.size() != n || vs.size() != n || ms.size() != n) return out;
+  std::vector<size_t> batch;
+  curves::Bytes sb, rb, kb, mb;
+  for (size_t b = 0; b < n; ++b) {
+    if (sigmas[b].curve != curve || sigmas[b].group != BGLS_G1 || us[b].curve != curve || us[b].group != BGLS_G2 || vs[b].curve != curve ||
+        vs[b].group != BGLS_G2 || rs[b].size() != 32 || ms[b].size() != 32)
+      continue;
+    batch.push_back(b);
+    sb.insert(sb.end(), sigmas[b].raw.begin(), sigmas[b].raw.end());
+    rb.insert(rb.end(), rs[b].begin(), rs[b].end());
+    kb.insert(kb.end(), us[b].raw.begin(), us[b].raw.end());
+    kb.insert(kb.end(), vs[b].raw.begin(), vs[b].raw.end());
+    mb.insert(mb.end(), ms[b].begin(), ms[b].end());
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = bgls_bb_verify_batch(curve->id, sb.data(), rb.data(), kb.data(), mb.data(), batch.size(), verdicts.data(), nullptr);
+  if (rc < 0 && batch.size() > 1) {
+    for (size_t b : batch) out[b] = bb_verify_batch(curve, {sigmas[b]}, {rs[b]}, {us[b]}, {vs[b]}, {ms[b]})[0];
+    return out;
+  }
+  for (size_t i = 0; i < batch.size(); ++i) out[batch[i]] = rc >= 0 && verdicts[i] == 1;
+  return out;
+}
+}  // namespace bgls

@@ -131,6 +131,20 @@ int bgls_verify_multi_batch(int curve, const uint8_t* sigs, const uint8_t* keys,
  * Returns the number of accepted sets (>= 0) or < 0. */
 int bgls_verify_multi_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
                            const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out);
+/* n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one set of launches: Boneh-Boyen signatures, item b is the signature
+ * (sigmas[b], rs[b]) on the message scalar ms[b] under the key (U_b, V_b).
+ * sigmas: n G1 points; rs, ms: n x 32-byte big-endian magnitudes; keys: n x (U || V), 2 G2 points each.
+ * verdicts[b] = 1 / 0; gt_out: NULL or n GT elements, gt_out[b] = e(sigma_b, Q_b), Q_b = m_b g2 + U_b + r_b V_b, byte-equal to
+ * bgls_pair(sigma_b, Q_b); item b is accepted iff gt_out[b] equals bgls_pair(g1, g2) (GetGT()).
+ * Scalars are used as the given 256-bit magnitudes, unreduced (as bgls_scale_points).  Q_b is the exact point for every on-curve
+ * key, inside the order-r subgroup or not: keys are constructed Points, as for every Verify* call (see above bgls_verify_aggregate).
+ * A sigma, U or V at infinity, a zero scalar or Q_b at infinity give a verdict (e(inf, Q) = e(sigma, inf) = 1: rejected).  A
+ * non-canonical or off-curve sigma, U or V ANYWHERE, or a degenerate point step, fails the whole call with BGLS_ERR_ENCODING and
+ * leaves verdicts undefined.  n == 0 returns 0; n at or above 2^30 is BGLS_ERR_ARG.  The hashed form (VerifyHashed) is host work:
+ * m = blake2b-256(msg) mod r.
+ * Returns the number of accepted items (>= 0) or < 0. */
+int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms,
+                         size_t n, uint8_t* verdicts, uint8_t* gt_out);
 /* AggregatePoints (curves/curve.go:73-121) over n_sets sets in one pass: out[b] = sum of pts[set_off[b] .. set_off[b+1])
  * (an empty set gives the point at infinity).  What the n_sets AggregateKeys calls of blsKosk.go:128-131 cost. */
 int bgls_aggregate_sets(int curve, int group, const uint8_t* pts, const uint64_t* set_off, size_t n_sets, uint8_t* out);
@@ -345,6 +359,10 @@ int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void
 int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
                                size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
                                uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_bb_verify_batch with its inputs on the device (same layouts).  Same semantics and return value; synchronises `stream`
+ * (NULL: the context's stream) before it returns. */
+int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms,
+                             size_t n, uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* bgls_verify_aggregate_batch with signatures, keys and messages on the device: d_sigs = n_inst G1 points, d_keys = inst_off[n_inst]
  * G2 points, message i at d_msgs + i * msg_stride (msg_len bytes).  inst_off stays a HOST array (it plans the launches).  Same
  * semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns.  Every batch runs the Miller
