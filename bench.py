@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: aggregate-verify signer-pairs/sec (BASELINE.json `metric`: alt-bn128 & BLS12-381).
 
-  python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full]        (N > 1: launched by torch.distributed.run)
 
 One "step" = one complete VerifyAggregateSignature over the resident batch: duplicate-message scan, n hash-to-G1, n+1
 Miller loops, GT product, ONE final exponentiation, compare with 1 -- everything bgls/bgls.go:94-119 does, inputs already
@@ -10,18 +10,24 @@ in HBM (keys as the reference's wire-format bytes, 64-byte messages as in bgls/b
 Headline (`value`): alt-bn128, ONE 2^20-signer batch (north_star's target size) cut into contiguous signer ranges over the
 N GPUs (strong scaling: 2^20 / N signers per GPU): partial Miller product per rank, one all-gather of the 384-byte
 partials + status words, local combine + final exponentiation on every rank (bgls_amd/sharding.py; BASELINE config 5's
-decomposition).  The same JSON line carries, under "records", the other BASELINE configs measured in the same process:
-BLS12-381 at 2^20 (every N), and at N = 1 both curves at 2^16 (configs 2, 3), the alt-bn128 multi-signature check at 2^20
-signers (config 4) and the reference's own CPU-runnable shape, alt-bn128 n = 64 (config 1).  Every record has the headline's
-schema: value, ms_per_step (median / min over the repetitions), roofline {frac, kernel, launch_ms, traffic}, and
-cpu_baseline where one was taken.
+decomposition).
+
+A plain run does only what the headline needs: it builds the instance, checks that it verifies, warms up, times the steps
+and prints the line; its "roofline" and "cpu_baseline" are null and "records" is empty.  `--full` adds everything else,
+measured in the same process: the negative controls of the correctness gate (a tampered message, and for N > 1 a duplicate
+message across shards), the headline's steps once more with the messages copied from the host, the roofline (which probes
+the multiplier's peak), the CPU baselines, and under "records" the other BASELINE configs: BLS12-381 at 2^20 (every N), and
+at N = 1 both curves at 2^16 (configs 2, 3), the alt-bn128 multi-signature check at 2^20 signers (config 4) and the
+reference's own CPU-runnable shape, alt-bn128 n = 64 (config 1).  Every record has the headline's schema: value,
+ms_per_step (median / min over the repetitions), roofline {frac, kernel, launch_ms, traffic}, and cpu_baseline where one
+was taken.
 
 Two further records, "<curve>_<n>_prepared_keys", time the same batches against PREPARED key sets (bgls_keys_upload with
 BGLS_KEYS_PREPARE: the keys' Miller line functions are computed once at upload and stay in HBM); they are secondary,
 labelled figures -- the headline and the BASELINE records always include the G2 point steps in the timed region.
 
-`python bench.py --only aggregate --curve bls12 --n 65536 --in-flight 1` etc. run a single record (profiling runs;
-`--prepared` for the prepared-key-set path).
+`python bench.py --only aggregate --curve bls12 --n 65536 --in-flight 1` etc. run a single record with everything it
+measures, as `--full` would (profiling runs; `--prepared` for the prepared-key-set path).
 
 `--dump-outputs DIR` writes what the headline's last timed step returned to its caller (verdict, status word, partial Miller
 product) as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
@@ -414,11 +420,14 @@ def dump_outputs(outdir, arrays):
 PREPARED_FPMUL = {0: 88 * 40 + 64 * 72 // 24, 1: 69 * 40 + 64 * 72 // 24}    # per pair: lines x (2 Fp2 products on 6 lanes + 4 scalings) + squarings / 24
 
 
-def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, in_flight, throughput, label, with_h2d=True, prepared=False, dump=None):
+def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, in_flight, throughput, label, with_h2d=True, prepared=False, dump=None,
+                    full=True):
     """VerifyAggregateSignature over an n_total-signer batch of which this rank holds inst['n_local'] signers (the first
     n_local of `inst`).  Returns the record dict on rank 0 (None elsewhere).  `dump` (a dict) receives what the last timed
-    step returned to its caller (see timed_outputs)."""
+    step returned to its caller (see timed_outputs).  full = False: only the timed steps and what they need -- no negative
+    controls, no message-H2D leg, no roofline (its peak probe runs kernels of its own)."""
     cid, fp = inst["cid"], inst["fp"]
+    with_h2d = with_h2d and full
     gtb = 12 * fp
     n = inst["n_local"]
     t_keys = torch.frombuffer(bytearray(inst["keys"][:n * 4 * fp]), dtype=torch.uint8).to(dev)
@@ -511,17 +520,19 @@ def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, i
             dist.barrier()
         torch.cuda.synchronize()
 
-    # correctness gate: the valid instance verifies, one flipped message bit rejects
+    # correctness gate: the valid instance verifies (always: it is also the first call, which loads the kernels), one flipped
+    # message bit rejects
     if one() != 1:
         raise RuntimeError("valid instance rejected (%s)" % label)
-    bad = t_msgs.clone()
-    if rank == world - 1:
-        bad[64 * (n // 2) + 3] ^= 0x20
-    torch.cuda.synchronize()              # `bad` was written on torch's default stream, the lanes have their own
-    if one(bad) != 0:
-        raise RuntimeError("tampered instance accepted (%s)" % label)
-    del bad
-    if world > 1:                         # a duplicate that straddles two shards: found through the digests, settled by the exact scan
+    if full:
+        bad = t_msgs.clone()
+        if rank == world - 1:
+            bad[64 * (n // 2) + 3] ^= 0x20
+        torch.cuda.synchronize()          # `bad` was written on torch's default stream, the lanes have their own
+        if one(bad) != 0:
+            raise RuntimeError("tampered instance accepted (%s)" % label)
+        del bad
+    if full and world > 1:                # a duplicate that straddles two shards: found through the digests, settled by the exact scan
         dup = t_msgs.clone()
         if rank == 0:
             dup[0:64] = 0xA5
@@ -583,10 +594,40 @@ def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, i
     if rank != 0:
         return None
 
-    peak = pinned_peak(lib)
     per_step = sorted(r / steps for r in regions)
     med = statistics.median(per_step)
     value = n_total / med
+    rec = {
+        "metric": "aggregate-verify signer-pairs/sec", "value": value, "unit": "signer-pairs/s",
+        "ms_per_step": med * 1e3, "ms_per_step_min": per_step[0] * 1e3, "ms_per_step_all": [p * 1e3 for p in per_step],
+        "steps": steps, "warmup": warmup, "repetitions": reps, "n_gpus": world, "dtype": "u32", "data": "synthetic",
+        "config": {"workload": "%s VerifyAggregateSignature, one %d-signer batch, %d signers per GPU, distinct 64-byte messages, keys and "
+                               "messages resident in HBM" % (CNAME[cid], n_total, n),
+                   "curve": CNAME[cid], "signers": n_total, "signers_per_gpu": n, "in_flight": L,
+                   "parallelism": "contiguous signer ranges x%d + one all-gather of GT partials and status words" % world},
+        "roofline": aggregate_roofline(lib, cid, n, world, value, med, stages_excl, use_tp, prepared) if full else None,
+        "sequential": {"ms_per_step_median": statistics.median(seq), "ms_per_step_min": min(seq), "value": n_total / (statistics.median(seq) * 1e-3),
+                       "note": "one verification at a time (the %d warm-up steps), end to end" % len(seq)},
+        "stage_ms_per_step": {k: (v[0] / max(v[1], 1)) for k, v in stages.items()},
+        "stage_ms_exclusive": {k: (v[0] / max(v[1], 1)) for k, v in stages_excl.items()},
+    }
+    if prepared:
+        rec["config"]["workload"] = ("%s VerifyAggregateSignature against a PREPARED resident key set (bgls_keys_upload with BGLS_KEYS_PREPARE: the line "
+                                     "functions of every key and Miller step computed at upload, %.0f ms, untimed), one %d-signer batch, distinct 64-byte "
+                                     "messages resident in HBM" % (CNAME[cid], upload_s * 1e3, n_total))
+        rec["prepared_upload_ms"] = upload_s * 1e3
+    if h2d_elapsed is not None:
+        rec["with_message_h2d"] = {"value": n_total * steps / h2d_elapsed, "ms_per_step": h2d_elapsed / steps * 1e3,
+                                   "note": "the same steps with the %d MiB of messages copied from pinned host memory inside every step "
+                                           "(keys stay resident, SURVEY 8d timing protocol)" % (n * 64 >> 20)}
+    return rec
+
+
+def aggregate_roofline(lib, cid, n, world, value, med, stages_excl, use_tp, prepared):
+    """The roofline of an aggregate-verification record on n signers per GPU: the dominant kernel's algorithmic MACs over the
+    median timed step (`med`, seconds) and over the warm-up steps' own HIP events (`stages_excl`), against the multiplier's
+    probed peak (pinned_peak)."""
+    peak = pinned_peak(lib)
     launches_per_step = 1 if prepared else (n + LAUNCH_PAIRS - 1) // LAUNCH_PAIRS
     pairs_per_launch = n if prepared else min(n, LAUNCH_PAIRS)
     macs_per_launch = (pairs_per_launch + 1) * (PREPARED_FPMUL if prepared else MILLER_FPMUL)[cid] * MAC_PER_FPMUL[cid]
@@ -608,52 +649,31 @@ def bench_aggregate(lib, dev, inst, n_total, rank, world, steps, warmup, reps, i
     if prepared:
         kernel_excl = kernel_timed = "k_fold_prep<%s>" % ("BN254" if cid == 0 else "BLS381")
     traffic, tdet = traffic_for(kernel_timed.split("<")[0] + "_" + CNAME[cid])
-    rec = {
-        "metric": "aggregate-verify signer-pairs/sec", "value": value, "unit": "signer-pairs/s",
-        "ms_per_step": med * 1e3, "ms_per_step_min": per_step[0] * 1e3, "ms_per_step_all": [p * 1e3 for p in per_step],
-        "steps": steps, "warmup": warmup, "repetitions": reps, "n_gpus": world, "dtype": "u32", "data": "synthetic",
-        "config": {"workload": "%s VerifyAggregateSignature, one %d-signer batch, %d signers per GPU, distinct 64-byte messages, keys and "
-                               "messages resident in HBM" % (CNAME[cid], n_total, n),
-                   "curve": CNAME[cid], "signers": n_total, "signers_per_gpu": n, "in_flight": L,
-                   "parallelism": "contiguous signer ranges x%d + one all-gather of GT partials and status words" % world},
-        "roofline": {"bound": "valu-int32-mac", "kernel": kernel_timed, "peak": peak / 1e12, "unit": "TMAC/s",
-                     "achieved": macs_per_launch / shared_launch_s / 1e12, "frac": macs_per_launch / shared_launch_s / peak,
-                     "launch_ms": shared_launch_s * 1e3, "launches_per_step": launches_per_step, "macs_per_launch": macs_per_launch,
-                     "traffic": traffic, "traffic_detail": tdet,
-                     "exclusive": {"kernel": kernel_excl, "launch_ms": excl_launch_s * 1e3, "achieved": macs_per_launch / excl_launch_s / 1e12 if excl_launch_s else None,
-                                   "frac": macs_per_launch / excl_launch_s / peak if excl_launch_s else None,
-                                   "note": "HIP events around the Miller stage of the %d one-at-a-time warm-up steps, divided by its launches" % ex_cnt},
-                     "hbm_side": {"achieved": pairs_per_launch * ALGO_BYTES_PER_PAIR[cid] / shared_launch_s / 1e9, "peak": 8000.0, "unit": "GB/s",
-                                  "note": "algorithmic bytes of one Miller launch (key + message per pair) / launch_ms"},
-                     "whole_path_frac": value / world * PAIR_FPMUL[cid] * MAC_PER_FPMUL[cid] / peak,
-                     "note": "integer bignum path bounded by v_mad_u64_u32 issue, not HBM or MFMA (SURVEY 8d); achieved = algorithmic MACs of one "
-                             "launch ((pairs + 1) x %d Fp multiplications x %d MAC) / launch_ms; launch_ms = median timed region / launches in it"
-                             % (MILLER_FPMUL[cid], MAC_PER_FPMUL[cid])},
-        "sequential": {"ms_per_step_median": statistics.median(seq), "ms_per_step_min": min(seq), "value": n_total / (statistics.median(seq) * 1e-3),
-                       "note": "one verification at a time (the %d warm-up steps), end to end" % len(seq)},
-        "stage_ms_per_step": {k: (v[0] / max(v[1], 1)) for k, v in stages.items()},
-        "stage_ms_exclusive": {k: (v[0] / max(v[1], 1)) for k, v in stages_excl.items()},
-    }
+    roof = {"bound": "valu-int32-mac", "kernel": kernel_timed, "peak": peak / 1e12, "unit": "TMAC/s",
+            "achieved": macs_per_launch / shared_launch_s / 1e12, "frac": macs_per_launch / shared_launch_s / peak,
+            "launch_ms": shared_launch_s * 1e3, "launches_per_step": launches_per_step, "macs_per_launch": macs_per_launch,
+            "traffic": traffic, "traffic_detail": tdet,
+            "exclusive": {"kernel": kernel_excl, "launch_ms": excl_launch_s * 1e3, "achieved": macs_per_launch / excl_launch_s / 1e12 if excl_launch_s else None,
+                          "frac": macs_per_launch / excl_launch_s / peak if excl_launch_s else None,
+                          "note": "HIP events around the Miller stage of the %d one-at-a-time warm-up steps, divided by its launches" % ex_cnt},
+            "hbm_side": {"achieved": pairs_per_launch * ALGO_BYTES_PER_PAIR[cid] / shared_launch_s / 1e9, "peak": 8000.0, "unit": "GB/s",
+                         "note": "algorithmic bytes of one Miller launch (key + message per pair) / launch_ms"},
+            "whole_path_frac": value / world * PAIR_FPMUL[cid] * MAC_PER_FPMUL[cid] / peak,
+            "note": "integer bignum path bounded by v_mad_u64_u32 issue, not HBM or MFMA (SURVEY 8d); achieved = algorithmic MACs of one "
+                    "launch ((pairs + 1) x %d Fp multiplications x %d MAC) / launch_ms; launch_ms = median timed region / launches in it"
+                    % (MILLER_FPMUL[cid], MAC_PER_FPMUL[cid])}
     if prepared:
-        rec["config"]["workload"] = ("%s VerifyAggregateSignature against a PREPARED resident key set (bgls_keys_upload with BGLS_KEYS_PREPARE: the line "
-                                     "functions of every key and Miller step computed at upload, %.0f ms, untimed), one %d-signer batch, distinct 64-byte "
-                                     "messages resident in HBM" % (CNAME[cid], upload_s * 1e3, n_total))
-        rec["roofline"]["note"] = ("prepared path: no point steps inside the timed region; achieved = (pairs + 1) x %d Fp multiplications (per pair: 88 / 69 lines x "
-                                   "(2 Fp2 products on 6 lanes + 4 scalings) + the shared squarings) x %d MAC / launch_ms" % (PREPARED_FPMUL[cid], MAC_PER_FPMUL[cid]))
-        rec["prepared_upload_ms"] = upload_s * 1e3
-        rec["roofline"].pop("whole_path_frac", None)      # the whole-path work model counts point steps this path does not execute
+        roof["note"] = ("prepared path: no point steps inside the timed region; achieved = (pairs + 1) x %d Fp multiplications (per pair: 88 / 69 lines x "
+                        "(2 Fp2 products on 6 lanes + 4 scalings) + the shared squarings) x %d MAC / launch_ms" % (PREPARED_FPMUL[cid], MAC_PER_FPMUL[cid]))
+        roof.pop("whole_path_frac", None)      # the whole-path work model counts point steps this path does not execute
     if cid == 1:
         # SURVEY 8d's 7 900 m per BLS12-381 hash is the REFERENCE algorithm's count (modular-exponentiation Legendre tests and inversions);
         # the shipped hash executes ~3 000 m per message (binary Jacobi symbols, fractions instead of inversions), so value x survey work / peak
         # would read above 1 -- "not doing the work" (verdict r4).  The per-kernel fractions above count executed algorithmic work; this one is dropped.
-        rec["roofline"].pop("whole_path_frac", None)
-    if h2d_elapsed is not None:
-        rec["with_message_h2d"] = {"value": n_total * steps / h2d_elapsed, "ms_per_step": h2d_elapsed / steps * 1e3,
-                                   "note": "the same steps with the %d MiB of messages copied from pinned host memory inside every step "
-                                           "(keys stay resident, SURVEY 8d timing protocol)" % (n * 64 >> 20)}
-    if not prepared:                      # the evidence run's counters are those of the un-prepared Miller kernel
-        cycle_roofline(rec["roofline"])
-    return rec
+        roof.pop("whole_path_frac", None)
+    if not prepared:                           # the evidence run's counters are those of the un-prepared Miller kernel
+        cycle_roofline(roof)
+    return roof
 
 
 def bench_multisig(lib, dev, inst, n, steps, warmup, reps, in_flight, key_set=False):
@@ -939,10 +959,13 @@ def main():
     ap.add_argument("--n", "--signers", dest="n", type=int, default=1 << 20, help="signers of the headline batch (whole job)")
     ap.add_argument("--curve", default="altbn128", choices=["altbn128", "bls12"])
     ap.add_argument("--in-flight", type=int, default=8, help="verifications kept in flight (1 = strictly sequential, max 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the gate's negative controls, the message-H2D leg, the roofline, the CPU baselines and the other records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-throughput-mode", action="store_true", help="keep the 64-pairing Miller kernel also when launches overlap")
-    ap.add_argument("--only", default=None, choices=["aggregate", "multisig", "multisig_batch", "small"], help="run ONE record (profiling runs): --curve, --n apply")
-    ap.add_argument("--no-records", action="store_true", help="headline only")
+    ap.add_argument("--only", default=None, choices=["aggregate", "multisig", "multisig_batch", "small"],
+                    help="run ONE record with everything it measures (profiling runs): --curve, --n apply")
+    ap.add_argument("--no-records", action="store_true", help="with --full: the headline record only")
     ap.add_argument("--prepared", action="store_true", help="with --only aggregate: verify against a prepared key set")
     ap.add_argument("--x60-mode", type=int, default=None, help="development: bgls_set_miller_shape(4, MODE) -- role / priority / block-form word of k_miller_x60")
     ap.add_argument("--key-set", action="store_true", help="with --only multisig: the keys are a resident key set (bgls_keys_upload) instead of wire bytes")
@@ -998,11 +1021,11 @@ def main():
     inst = shard_instance(cid, args.n, 0xB6150000 + 1 + cid)
     outputs = {} if args.dump_outputs is not None else None
     head = bench_aggregate(lib, dev, inst, args.n, rank, world, args.steps, args.warmup, args.reps, args.in_flight, tp, "headline",
-                           prepared=args.prepared and args.only == "aggregate", dump=outputs)
+                           prepared=args.prepared and args.only == "aggregate", dump=outputs, full=args.full or args.only is not None)
     if outputs is not None and rank == 0:
         dump_outputs(args.dump_outputs, outputs)
     records = {}
-    if args.only is None and not args.no_records:
+    if args.full and args.only is None and not args.no_records:
         other = 1 - cid
         oinst = shard_instance(other, args.n, 0xB6150000 + 1 + other)
         r = bench_aggregate(lib, dev, oinst, args.n, rank, world, max(2, args.steps // 2), 1, args.reps, args.in_flight, tp, CNAME[other], with_h2d=False)
@@ -1036,7 +1059,7 @@ def main():
                             records[key]["cpu_baseline"] = cb
                     if c_ == cid:
                         head["cpu_baseline"] = cb
-    elif world == 1 and not args.no_cpu_baseline and args.only is None:
+    elif args.full and world == 1 and not args.no_cpu_baseline and args.only is None:
         head["cpu_baseline"] = cpu_baseline(cid, inst, lib)
     if rank == 0:
         full = dict(head)

@@ -78,6 +78,17 @@ def test_cpu_baseline_is_not_capped_at_64_threads(monkeypatch):
     assert "sched_getaffinity" in src_small and "verify_aggregate" in src_small and "min(cores, n + 1)" in src_small
 
 
+def test_plain_run_line_is_complete():
+    """A run without --full has no roofline, CPU baseline or other records: its line carries the headline and those three empty."""
+    bench = _bench()
+    full = _canned_record(bench, "altbn128")
+    full.pop("cpu_baseline")
+    full.update({"roofline": None, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "records": {}})
+    rec = json.loads(bench.compact_line(full))
+    assert rec["value"] == 14234600.0 and rec["ms_per_step"] == 73.6661 and rec["unit"] == "signer-pairs/s" and rec["dtype"] == "u32"
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["records"] == {}
+
+
 def test_line_shrinks_rather_than_overflowing():
     bench = _bench()
     full = _canned_record(bench, "altbn128")

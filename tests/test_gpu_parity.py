@@ -505,15 +505,15 @@ def test_bucketed_digest_scan_at_adversarial_scale(gpu_lib):
 
 def test_bench_two_ranks_share_one_gpu():
     """The N > 1 path of bench.py end to end on real kernels: two ranks on cuda:0 exchanging over gloo
-    (BGLS_BENCH_SHARE_GPU=1) -- shard ranges, global duplicate scan, partial + status all-gather, final verification and
-    the tampered-message gate all run; only the numbers are meaningless."""
+    (BGLS_BENCH_SHARE_GPU=1) -- shard ranges, global duplicate scan, partial + status all-gather, final verification and,
+    with --full, the tampered-message gate and the other records all run; only the numbers are meaningless."""
     import json, os, socket, subprocess, sys
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ); env["BGLS_BENCH_SHARE_GPU"] = "1"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--signers", "8192", "--no-cpu-baseline", "--reps", "1"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
+                          "--signers", "8192", "--no-cpu-baseline", "--reps", "1", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=root)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.stdout[-800:], out.stderr[-1500:])
     assert out.stdout.rstrip().splitlines()[-1] == lines[0] and len(lines[0]) < 4096      # the compact record is the LAST line
@@ -553,6 +553,27 @@ def test_bench_dump_outputs(tmp_path):
     assert a["gt_partial"].dtype == np.float32 and a["gt_partial"].shape == (12 * 32,) and a["gt_partial"].any()
     for k in a:
         assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+
+
+def test_bench_plain_run_is_headline_only():
+    """bench.py without --full: the headline's figure and nothing else -- no roofline, no CPU baseline, no other records, no
+    message-H2D leg -- while value and ms_per_step keep their meaning (signers / median step time)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--signers", "4096", "--steps", "3", "--warmup", "1",
+                          "--reps", "1"], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, (out.stdout[-800:], out.stderr[-1500:])
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and out.stdout.rstrip().splitlines()[-1] == lines[0]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "aggregate-verify signer-pairs/sec" and rec["unit"] == "signer-pairs/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "u32" and rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] * 1e-3 / 4096 - 1) < 1e-4
+    assert rec["roofline"] is None and rec["cpu_baseline"] is None and rec["records"] == {}
+    det = [l for l in out.stdout.splitlines() if l.startswith("DETAIL {")]
+    assert len(det) == 1
+    full = json.loads(det[0][len("DETAIL "):])
+    assert "with_message_h2d" not in full and full["roofline"] is None and full["records"] == {}
 
 
 def test_two_contexts_in_flight(gpu_lib, curve):
