@@ -48,6 +48,10 @@ SIGNATURES = {
     "bgls_aggregate_signatures_hae": (ci, [ci, u8p, u8p, sz, u8p]),
     "bgls_verify_multi_hae": (ci, [ci, u8p, u8p, sz, u8p, sz]),
     "bgls_verify_aggregate_hae": (ci, [ci, u8p, u8p, u8p, u64p, sz]),
+    "bgls_verify_multi_hae_sets": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p, u8p]),
+    "bgls_verify_multi_hae_sets_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, u8p, vp]),
+    "bgls_hae_exponents_sets": (ci, [ci, u8p, u64p, sz, u8p]),
+    "bgls_set_hae_root_host_min": (ci, [sz]),
     "bgls_verify_multi_multiplicity": (ci, [ci, u8p, u8p, ctypes.POINTER(ctypes.c_int64), sz, u8p, sz]),
     "bgls_hash_to_g1": (ci, [ci, u8p, u64p, sz, u8p]),
     "bgls_aggregate_points": (ci, [ci, ci, u8p, sz, u8p]),

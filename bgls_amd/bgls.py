@@ -315,6 +315,35 @@ def VerifyMultiSignatureWithHAE(curve, aggsig, pubkeys, msg):        # bgls/blsH
     return rc == 1
 
 
+def VerifyMultiSignaturesWithHAE(curve, aggsigs, pubkeys, msgs):
+    """len(aggsigs) independent VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58) in one bgls_verify_multi_hae_sets call: a list
+    of bools, one per set.  A set that is not made of Points of this curve (a nil or foreign signature, a foreign key, a KeySet) gets
+    what VerifyMultiSignatureWithHAE says about it alone; a call that fails as a whole is settled set by set."""
+    if not (len(aggsigs) == len(pubkeys) == len(msgs)):
+        raise ValueError("aggsigs, pubkeys and msgs differ in length")
+    out = [False] * len(aggsigs)
+    batch = []
+    for b, (sig, keys) in enumerate(zip(aggsigs, pubkeys)):
+        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet)
+                and _g2_keys_ok(curve, keys)):
+            batch.append(b)
+        else:
+            out[b] = VerifyMultiSignatureWithHAE(curve, sig, keys, bytes(msgs[b]))
+    if not batch:
+        return out
+    key_off = (ctypes.c_uint64 * (len(batch) + 1))()
+    for i, b in enumerate(batch):
+        key_off[i + 1] = key_off[i] + len(pubkeys[b])
+    ms = [bytes(msgs[b]) for b in batch]
+    verdicts = (ctypes.c_uint8 * len(batch))()
+    rc = _lib.load().bgls_verify_multi_hae_sets(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
+                                                _lib.buf(b"".join(k.raw for b in batch for k in pubkeys[b])), key_off, len(batch),
+                                                _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None, None)
+    for i, b in enumerate(batch):
+        out[b] = verdicts[i] == 1 if rc >= 0 else VerifyMultiSignatureWithHAE(curve, aggsigs[b], pubkeys[b], ms[i])
+    return out
+
+
 def KoskVerifyMultiSignatureWithMultiplicity(curve, aggsig, keys, multiplicity, msg):   # bgls/blsKosk.go:137-150
     if multiplicity is None:
         return KoskVerifyMultiSignature(curve, aggsig, keys, msg)

@@ -112,6 +112,54 @@ int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys
   DISPATCH(curve, verify_multi_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+// offsets of a batch of HAE sets: monotone, below 2^30 keys in all and 2^28 per set
+static int hae_sets_off_ok(const uint64_t* key_off, size_t n_sets) {
+  for (size_t b = 0; b < n_sets; ++b) {
+    if (key_off[b + 1] < key_off[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
+    if (key_off[b + 1] - key_off[b] >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (blsHAE.go:81)");
+  }
+  if (key_off[n_sets] - key_off[0] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  return 0;
+}
+
+int bgls_verify_multi_hae_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
+                               const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) try {
+  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (!key_off || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  for (size_t b = 0; b < n_sets; ++b)
+    if (msg_off[b + 1] < msg_off[b]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
+  int rc;
+  if ((rc = hae_sets_off_ok(key_off, n_sets))) return rc;
+  if (n_sets == 0) return 0;
+  if (!sigs || !verdicts || (msg_off[n_sets] && !msg_blob) || (key_off[n_sets] > key_off[0] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_multi_hae_sets_t<CV>(sigs, keys, key_off, n_sets, msg_blob, msg_off, verdicts, apk_out, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
+                                   const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out,
+                                   void* stream) try {
+  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets == 0) return 0;
+  if (!d_sigs || !d_key_off || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_multi_hae_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, apk_out, gt_out,
+                                                  stream));
+} BGLS_ABI_GUARD
+
+int bgls_hae_exponents_sets(int curve, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out) try {
+  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (!key_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = hae_sets_off_ok(key_off, n_sets))) return rc;
+  if (n_sets == 0) return 0;
+  if (key_off[n_sets] > key_off[0] && (!keys || !t_out)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, hae_exponents_sets_t<CV>(keys, key_off, n_sets, t_out));
+} BGLS_ABI_GUARD
+
+int bgls_set_hae_root_host_min(size_t n) try {
+  g_hae_root_host_min.store(n);
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, uint8_t* verdicts,
                          uint8_t* gt_out) try {
   if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");

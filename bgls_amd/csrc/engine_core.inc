@@ -57,12 +57,14 @@ struct SideJoin {
 // Largest batch one call accepts: the duplicate table (2n rounded up to a power of two, u32 slots), the hashing work
 // lists (u32 indices) and the grid computations all assume n < 2^30.
 constexpr size_t MAX_BATCH = (size_t)1 << 30;
+// keys per set of the batched HAE calls: the XOF length 16 n is a uint32 (blsHAE.go:81)
+constexpr size_t HAE_MAX_SET = (size_t)1 << 28;
 // batches up to this many pairings take the latency form of the Miller loop (one block per pairing, k_miller_lat)
 constexpr size_t LAT_MAX = 128;
 
 // workspace slots
 enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
-       WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_NUM };
+       WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_HAE_NODES, WS_NUM };
 
 struct Ctx {
   std::mutex mu;
@@ -259,8 +261,10 @@ constexpr int miller_dbg() { return 0; }
 // ST_SUM is opened ONCE per key sum (main pass + tree + conversion); ST_SUM_MAIN brackets the main-pass kernel alone, inside it
 // ST_SCATTER and ST_EPI are opened by the batch of independent verifications only (Engine::miller_product_batch): the padded layout
 // of its pairs and its batched epilogue; ST_BB_KEYS by the batched Boneh-Boyen verification only (Engine::miller_bb: its Q_b = m_b g2 + U_b + r_b V_b)
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_NUM };
-const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys"};
+// ST_HAE_KEYS by the batched HAE multi-signatures only (bgls_verify_multi_hae_sets: the roots, the XOF expansion and the weighted main pass)
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_NUM };
+const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys",
+                                         "hae_keys"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -285,7 +289,7 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -962,8 +966,14 @@ struct Engine {
     if ((rc = c.get(WS_JAC_B, (written / 2 + 2) * JB, &jb))) return rc;
     if (group == BGLS_G2 && sum_pairs()) kl::sumpairseg_main<C>(st, d_pts, d_off, nsets, (unsigned)P, ja, d_flags);
     else kl::sumseg_main<C>(st, group, d_pts, d_off, nsets, (unsigned)P, ja, d_flags);
-    void *a = ja, *b = jb;
-    size_t p = pairs ? P / 32 : P, cnt = written;
+    sum_sets_tree(st, group, ja, jb, pairs ? P / 32 : P, nsets, d_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // The levels above a segmented main pass (sum_sets, the weighted sums of bgls_verify_multi_hae_sets): a holds nsets * p Jacobian
+  // partials, set-major, p a power of two -- so no level pairs two sets; b has room for half of them.  The nsets sums to d_out as wire bytes.
+  static void sum_sets_tree(hipStream_t st, int group, void* a, void* b, size_t p, size_t nsets, uint8_t* d_out) {
+    size_t cnt = nsets * p;
     while (p > 1) {
       if (group == BGLS_G2 && cnt <= 8192) {
         kl::sum_coop<C>(st, a, cnt, b);
@@ -975,13 +985,9 @@ struct Engine {
         kl::sum_wave<C>(st, group, a, cnt, b);
         p /= 64; cnt /= 64;
       }
-      void* t = a;
-      a = b;
-      b = t;
+      std::swap(a, b);
     }
     kl::jac_to_bytes<C>(st, group, a, nsets, d_out);
-    HIPCHK(hipGetLastError());
-    return 0;
   }
   // the same sum left in Jacobian form at d_jac (multi-device key sums exchange projective partials, SURVEY 8e);
   // n == 0 gives the point at infinity (all-zero record: Z = 0)

@@ -275,13 +275,13 @@ int aggregate_sets_t(int group, const uint8_t* pts, const uint64_t* set_off, siz
   return flags_to_rc(f);
 }
 
-// n_sets independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one set of launches: every key sum in one pass
-// (Engine::sum_sets), then Engine::miller_multi_sets and one final exponentiation per set in ONE launch; verdicts[b] = 1 / 0, returns the
-// number of accepted sets.  d_key_off: n_sets + 1 device offsets, already checked (monotone, no set above max_set).  An encoding or
-// hashing failure anywhere fails the whole call with the single call's code.
-template <class C>
-int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, const uint64_t* d_key_off, size_t n_sets, size_t max_set,
-                          MsgView mv, uint8_t* verdicts, uint8_t* gt_out) {
+// The part of a batch of multi-signature sets that follows the key sums: sum_keys(d_apks, d_flags) leaves the n_sets key sums apk_b as wire
+// bytes at d_apks (encoding failures in d_flags); then Engine::miller_multi_sets and one final exponentiation per set in ONE launch.
+// verdicts[b] = 1 / 0, returns the number of accepted sets; apk_out / gt_out (nullable): the key sums / GT elements.  An encoding or hashing
+// failure anywhere fails the whole call with the single call's code.
+template <class C, class SumKeys>
+int verify_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, size_t n_sets, MsgView mv, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out,
+                    SumKeys&& sum_keys) {
   typedef Engine<C> E;
   if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
   // words: n_sets per-set flags (no duplicate rule: they stay zero), n_sets verdicts, the call's flag word
@@ -302,7 +302,7 @@ int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const u
     }
   } drain{st};
   HIPCHK(hipMemsetAsync(d_res, 0, (2 * n_sets + 1) * 4, st));
-  if ((rc = E::sum_sets(c, st, BGLS_G2, d_keys, d_key_off, n_sets, max_set, (uint8_t*)d_apks, d_flags))) return rc;   // apk_b = AggregateKeys(set b)
+  if ((rc = sum_keys((uint8_t*)d_apks, d_flags))) return rc;
   if ((rc = E::miller_multi_sets(c, st, d_sigs, (const uint8_t*)d_apks, mv, n_sets, (uint8_t*)d_part, d_flags))) return rc;
   {
     Scope sc(c, st, ST_FINAL);
@@ -312,6 +312,7 @@ int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const u
   std::vector<uint32_t> words(n_sets + 1);
   HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n_sets + 1) * 4, hipMemcpyDeviceToHost, st));
   if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n_sets * E::GTB, hipMemcpyDeviceToHost, st));
+  if (apk_out) HIPCHK(hipMemcpyAsync(apk_out, d_apks, n_sets * E::G2B, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   c.collect();
@@ -322,6 +323,16 @@ int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const u
     accepted += words[b] ? 1 : 0;
   }
   return accepted;
+}
+
+// n_sets independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one set of launches: every key sum in one pass
+// (Engine::sum_sets), then verify_sets_run.  d_key_off: n_sets + 1 device offsets, already checked (monotone, no set above max_set).
+template <class C>
+int verify_multi_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, const uint64_t* d_key_off, size_t n_sets, size_t max_set,
+                          MsgView mv, uint8_t* verdicts, uint8_t* gt_out) {
+  return verify_sets_run<C>(c, st, d_sigs, n_sets, mv, verdicts, nullptr, gt_out, [&](uint8_t* d_apks, uint32_t* d_flags) {
+    return Engine<C>::sum_sets(c, st, BGLS_G2, d_keys, d_key_off, n_sets, max_set, d_apks, d_flags);     // apk_b = AggregateKeys(set b)
+  });
 }
 
 template <class C>
@@ -1090,6 +1101,184 @@ int aggregate_signatures_hae_t(const uint8_t* sigs, const uint8_t* keys, size_t 
   HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return flags_to_rc(f);
+}
+
+// ---- n_sets VerifyMultiSignatureWithHAE calls in one set of launches (bgls_verify_multi_hae_sets) -------------------------------
+// Sets with more keys than this have their BLAKE2Xb root computed on the host by the host-pointer entries (bgls_set_hae_root_host_min;
+// tests pin both paths).  A root is one sequential compression chain, much slower on one GPU lane than on the host: the host takes the
+// few sets whose lone chain would hold up the batch (DESIGN.md, batched HAE multi-signatures).
+std::atomic<size_t> g_hae_root_host_min{2048};
+
+// The exponents of n_sets key sets (hashPubKeysToExponents per set, blsHAE.go:80-93), staged on the host: the node table of the XOF
+// expansion and the roots of the sets above host_min when the keys' host bytes are given (h_keys), else none.  koff: the n_sets + 1
+// offsets from 0, checked.  launch() then runs k_hae_root_seg and k_hae_expand_seg: set b's exponents at d_t + 16 koff[b].
+template <class C>
+struct HaeSets {
+  const uint8_t* d_keys;
+  const uint64_t* d_koff;
+  size_t n_sets, n_host = 0, n_nodes = 0, host_min = SIZE_MAX;
+  uint64_t* d_roots = nullptr;
+  uint32_t* d_nodes = nullptr;
+  uint8_t* d_t = nullptr;
+  int stage(Ctx& c, hipStream_t st, const uint64_t* koff, const uint8_t* h_keys, size_t host_min_) {
+    constexpr size_t G2B = Engine<C>::G2B;
+    if (h_keys) host_min = host_min_;
+    std::vector<uint64_t> host;                            // records of nine words: set index, root
+    std::vector<uint32_t> nodes;                           // (set, node index) per 64-byte XOF node
+    nodes.reserve(2 * (koff[n_sets] / 4 + n_sets));
+    for (size_t b = 0; b < n_sets; ++b) {
+      const size_t nk = koff[b + 1] - koff[b];
+      const uint32_t xof_len = (uint32_t)(16 * nk);
+      for (uint32_t i = 0; 64ull * i < xof_len; ++i) {
+        nodes.push_back((uint32_t)b);
+        nodes.push_back(i);
+      }
+      if (nk > host_min) {
+        host.push_back(b);
+        host.resize(host.size() + 8);
+        host_blake2::xb_root(h_keys + koff[b] * G2B, nk * G2B, xof_len, host.data() + host.size() - 8);
+      }
+    }
+    n_host = host.size() / 9;
+    n_nodes = nodes.size() / 2;
+    void *roots, *nd, *t;
+    int rc;
+    if ((rc = c.get(WS_HAE_ROOT, (n_sets * 8 + host.size()) * 8, &roots))) return rc;
+    if ((rc = c.get(WS_HAE_NODES, (nodes.size() + 2) * 4, &nd))) return rc;
+    if ((rc = c.get(WS_HAE_T, (koff[n_sets] + 1) * 16, &t))) return rc;
+    d_roots = (uint64_t*)roots;
+    d_nodes = (uint32_t*)nd;
+    d_t = (uint8_t*)t;
+    if (n_host) HIPCHK(hipMemcpyAsync(d_roots + n_sets * 8, host.data(), host.size() * 8, hipMemcpyHostToDevice, st));
+    if (n_nodes) HIPCHK(hipMemcpyAsync(d_nodes, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                       // host, nodes are locals
+    return 0;
+  }
+  void launch(hipStream_t st) const {
+    kl::hae_root_seg(st, d_keys, d_koff, n_sets, (unsigned)Engine<C>::G2B, host_min, d_roots + n_sets * 8, n_host, d_roots);
+    kl::hae_expand_seg(st, d_roots, d_nodes, n_nodes, d_koff, d_t);
+  }
+};
+
+// the key sums apk_b = sum_i t_i pk_i of the staged sets, as wire bytes to d_apks: k_hae_wsum_main (P partials per set), then the tree
+// levels of Engine::sum_sets.  A 128-bit multiplication costs about as much as 200 mixed additions, so P is planned for lanes rather
+// than for keys per lane: up to 2^18 lanes (four rounds of one wave per SIMD), a power of two no larger than the largest set.
+template <class C>
+int hae_sets_sum(Ctx& c, hipStream_t st, const HaeSets<C>& hs, size_t max_set, uint8_t* d_apks, uint32_t* d_flags) {
+  const size_t n_sets = hs.n_sets;
+  size_t P = 1;
+  while (2 * P <= max_set && n_sets * 2 * P <= ((size_t)1 << 18)) P *= 2;
+  const size_t written = n_sets * P, JB = kl::jac_bytes<C>(BGLS_G2);
+  if ((written + 1) * JB > ((size_t)8 << 30)) return fail(BGLS_ERR_ARG, "too many key sets for one call (cut the batch: at most 8 GiB of partial sums)");
+  void *ja, *jb;
+  int rc;
+  if ((rc = c.get(WS_JAC_A, (written + 1) * JB, &ja))) return rc;
+  if ((rc = c.get(WS_JAC_B, (written / 2 + 2) * JB, &jb))) return rc;
+  {
+    Scope sc(c, st, ST_HAE_KEYS);
+    hs.launch(st);
+    kl::hae_wsum_main<C>(st, hs.d_keys, hs.d_koff, hs.d_t, n_sets, (unsigned)P, ja, d_flags);
+  }
+  {
+    Scope sc(c, st, ST_SUM);
+    Engine<C>::sum_sets_tree(st, BGLS_G2, ja, jb, P, n_sets, d_apks);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// the keys of a host-pointer call on the device: keys key_off[0] .. key_off[n_sets] to *d_keys, the offsets relative to key_off[0] to
+// *d_koff and to rel (the host copy)
+template <class C>
+int upload_key_sets(Ctx& c, hipStream_t st, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, void** d_keys, void** d_koff,
+                    std::vector<uint64_t>& rel) {
+  const size_t k0 = key_off[0], nkeys = key_off[n_sets] - k0;
+  int rc;
+  if ((rc = c.get(WS_IN_B, (nkeys + 1) * Engine<C>::G2B, d_keys))) return rc;
+  if ((rc = c.get(WS_SEG_OFF, (n_sets + 1) * 8, d_koff))) return rc;
+  rel.resize(n_sets + 1);
+  for (size_t i = 0; i <= n_sets; ++i) rel[i] = key_off[i] - k0;
+  if (nkeys) HIPCHK(hipMemcpyAsync(*d_keys, keys + k0 * Engine<C>::G2B, nkeys * Engine<C>::G2B, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(*d_koff, rel.data(), (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  return 0;
+}
+
+template <class C>
+int hae_exponents_sets_t(const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out) {
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  hipStream_t st = c.stream;
+  void *d_keys, *d_koff;
+  std::vector<uint64_t> rel;
+  if ((rc = upload_key_sets<C>(c, st, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets};
+  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * Engine<C>::G2B, g_hae_root_host_min.load()))) return rc;
+  hs.launch(st);
+  HIPCHK(hipGetLastError());
+  if (rel[n_sets]) HIPCHK(hipMemcpyAsync(t_out + 16 * key_off[0], hs.d_t, rel[n_sets] * 16, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+template <class C>
+int verify_multi_hae_sets_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* blob, const uint64_t* off,
+                            uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+  hipStream_t st = c.stream;
+  size_t max_set = 0;
+  for (size_t i = 0; i < n_sets; ++i)
+    if (key_off[i + 1] - key_off[i] > max_set) max_set = key_off[i + 1] - key_off[i];
+  const size_t blob_len = off[n_sets];
+  void *d_sigs, *d_keys, *d_blob, *d_off, *d_koff;
+  std::vector<uint64_t> rel;
+  if ((rc = c.get(WS_IN_A, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
+  if ((rc = c.get(WS_IN_D, (n_sets + 1) * 8, &d_off))) return rc;
+  if ((rc = upload_key_sets<C>(c, st, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_sets * E::G1B, hipMemcpyHostToDevice, st));
+  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(d_off, off, (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets};
+  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * E::G2B, g_hae_root_host_min.load()))) return rc;   // also waits for rel's upload
+  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  return verify_sets_run<C>(c, st, (const uint8_t*)d_sigs, n_sets, mv, verdicts, apk_out, gt_out,
+                            [&](uint8_t* d_apks, uint32_t* d_flags) { return hae_sets_sum<C>(c, st, hs, max_set, d_apks, d_flags); });
+}
+
+template <class C>
+int verify_multi_hae_sets_dev_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs,
+                                size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream) {
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  int rc;
+  if ((rc = c.enter())) return rc;
+  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  // the offsets are the caller's device words: checked here (as bgls_verify_multi_sets_dev, and every set below 2^28 keys) before any
+  // launch reads the keys; the node table of the expansion is built from this copy
+  std::vector<uint64_t> koff(n_sets + 1);
+  HIPCHK(hipMemcpyAsync(koff.data(), d_key_off, (n_sets + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (koff[0] != 0) return fail(BGLS_ERR_ARG, "key_off must start at 0");
+  for (size_t b = 0; b < n_sets; ++b) {
+    if (koff[b + 1] < koff[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
+    if (koff[b + 1] - koff[b] > max_set) return fail(BGLS_ERR_ARG, "a set is larger than max_set");
+    if (koff[b + 1] - koff[b] >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (blsHAE.go:81)");
+  }
+  if (koff[n_sets] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (koff[n_sets] && !d_keys) return fail(BGLS_ERR_ARG, "NULL argument");
+  HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets};
+  if ((rc = hs.stage(c, st, koff.data(), nullptr, 0))) return rc;
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_sets_run<C>(c, st, (const uint8_t*)d_sigs, n_sets, mv, verdicts, apk_out, gt_out,
+                            [&](uint8_t* d_apks, uint32_t* d_flags) { return hae_sets_sum<C>(c, st, hs, max_set, d_apks, d_flags); });
 }
 
 // Marshal / Unmarshal* compressed branch over a batch.  alt-bn128: the reference's own 32 / 64-byte forms

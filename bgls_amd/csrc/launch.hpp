@@ -105,6 +105,17 @@ void bb_keys(hipStream_t st, const uint8_t* keys, const uint8_t* rs, const uint8
 template <class C> void bb_w_bytes(hipStream_t st, const Fp2<C>* w, size_t n, uint8_t* out);
 template <class C> void bb_verdicts(hipStream_t st, const uint8_t* gt, size_t n, uint32_t* verdicts);
 
+// ---- k_haesets.hip: batched hashed aggregation exponents and weighted key sums (bgls_verify_multi_hae_sets).  hae_root_seg: the BLAKE2Xb
+// root of every set with 1 .. host_min keys to roots + 8 b (keys: wire bytes of g2b each, key_off: n_sets + 1 device offsets), and the
+// n_host host-made roots (records of nine words: set index, root) to their places.  hae_expand_seg: nodes = n_nodes pairs (set, node
+// index), the exponents of set b to t + 16 key_off[b].  hae_wsum_main: P (a power of two) Jacobian partials of sum t_i pk_i per set to
+// out + b P, bad keys set FLAG_ENC.
+void hae_root_seg(hipStream_t st, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, unsigned g2b, size_t host_min, const uint64_t* host,
+                  size_t n_host, uint64_t* roots);
+void hae_expand_seg(hipStream_t st, const uint64_t* roots, const uint32_t* nodes, size_t n_nodes, const uint64_t* key_off, uint8_t* t);
+template <class C>
+void hae_wsum_main(hipStream_t st, const uint8_t* keys, const uint64_t* key_off, const uint8_t* t, size_t n_sets, unsigned P, void* out, uint32_t* flags);
+
 // prepared key sets (prepared.hpp): bytes per key of the line table, per pairing of the point table, per key of k_prepare's scratch
 struct PrepSizes { size_t line_bytes_per_key, point_bytes, tmp_bytes_per_key; };
 template <class C> PrepSizes prep_sizes();

@@ -612,6 +612,48 @@ func HipVerifyMultiSets(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, m
 	return ok
 }
 
+// HipVerifyMultiHAESets is len(aggsigs) independent bgls.VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58) in one
+// bgls_verify_multi_hae_sets call: ok[b] is set b's verdict.  A set that is not made of this curve's points gets HipVerifyMultiHAE's answer
+// alone; a call that fails as a whole is settled by the single calls.  Uncompiled text, as the rest of this file.
+func HipVerifyMultiHAESets(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, msgs [][]byte) []bool {
+	ok := make([]bool, len(aggsigs))
+	c, isHip := curve.(*hipCurve)
+	if !isHip || len(aggsigs) != len(pubkeys) || len(pubkeys) != len(msgs) {
+		return ok
+	}
+	var sb, kb, blob []byte
+	var batch []int
+	koff := []C.uint64_t{0}
+	moff := []C.uint64_t{0}
+	for b := range aggsigs {
+		s, isHipPoint := aggsigs[b].(*hipPoint)
+		one, ok3 := hipKeyBytes(c, pubkeys[b])
+		if !isHipPoint || s.group != C.BGLS_G1 || !ok3 {
+			ok[b] = HipVerifyMultiHAE(curve, aggsigs[b], pubkeys[b], msgs[b])
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		kb = append(kb, one...)
+		koff = append(koff, koff[len(koff)-1]+C.uint64_t(len(pubkeys[b])))
+		blob = append(blob, msgs[b]...)
+		moff = append(moff, C.uint64_t(len(blob)))
+	}
+	if len(batch) == 0 {
+		return ok
+	}
+	verdicts := make([]byte, len(batch))
+	rc := C.bgls_verify_multi_hae_sets(c.id, p(sb), p(kb), &koff[0], C.size_t(len(batch)), p(blob), &moff[0], p(verdicts), nil, nil)
+	for i, b := range batch {
+		if rc >= 0 {
+			ok[b] = verdicts[i] == 1
+		} else {
+			ok[b] = HipVerifyMultiHAE(curve, aggsigs[b], pubkeys[b], msgs[b])
+		}
+	}
+	return ok
+}
+
 // HipBBVerifyBatch is len(sigmas) independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one bgls_bb_verify_batch call: ok[b] is
 // item b's verdict, item b being the signature (sigmas[b], rs[b]) on the message scalar ms[b] under the key (us[b], vs[b]) (for
 // VerifyHashed pass blake2b256(msg) mod the order as ms[b]).  Negative scalars are reduced modulo the group order, as are magnitudes

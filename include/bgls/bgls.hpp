@@ -252,6 +252,38 @@ inline std::vector<bool> verifyMultiSignatures(const CurveSystem* curve, const s
   }
   return out;
 }
+// B independent VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58) in ONE bgls_verify_multi_hae_sets call: one bool per set.  A set
+// that is not made of this curve's points gets VerifyMultiSignatureWithHAE's answer alone; a call that fails as a whole is settled set by set.
+inline std::vector<bool> VerifyMultiSignaturesWithHAE(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                      const std::vector<Bytes>& msgs) {
+  std::vector<bool> out(aggsigs.size(), false);
+  if (keys.size() != aggsigs.size() || msgs.size() != aggsigs.size()) return out;
+  std::vector<size_t> batch;
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> koff(1, 0), moff(1, 0);
+  for (size_t b = 0; b < aggsigs.size(); ++b) {
+    Bytes one;
+    if (aggsigs[b].curve != curve || aggsigs[b].group != BGLS_G1 || !detail::g2_bytes(curve, keys[b], one)) {
+      out[b] = VerifyMultiSignatureWithHAE(curve, aggsigs[b], keys[b], msgs[b]);
+      continue;
+    }
+    batch.push_back(b);
+    sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+    kb.insert(kb.end(), one.begin(), one.end());
+    koff.push_back(koff.back() + keys[b].size());
+    blob.insert(blob.end(), msgs[b].begin(), msgs[b].end());
+    moff.push_back(blob.size());
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = bgls_verify_multi_hae_sets(curve->id, sb.data(), kb.data(), koff.data(), batch.size(), blob.data(), moff.data(), verdicts.data(), nullptr,
+                                            nullptr);
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const size_t b = batch[i];
+    out[b] = rc >= 0 ? verdicts[i] == 1 : VerifyMultiSignatureWithHAE(curve, aggsigs[b], keys[b], msgs[b]);
+  }
+  return out;
+}
 // B independent KoskVerifyMultiSignature calls (bgls/blsKosk.go:117-120): 0x01 prepended to every message
 inline std::vector<bool> KoskVerifyMultiSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
                                                    const std::vector<Bytes>& msgs) {

@@ -185,6 +185,23 @@ int bgls_verify_multi_hae(int curve, const uint8_t* sig, const uint8_t* keys, si
  * verifyAggSig with duplicate messages allowed. */
 int bgls_verify_aggregate_hae(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob,
                               const uint64_t* msg_off, size_t n);
+/* n_sets independent VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58,74-93) in one set of launches.  Set b is the signature
+ * sigs[b], the keys keys[key_off[b] .. key_off[b+1]) (wire bytes) and the message msg_blob[msg_off[b] .. msg_off[b+1]).
+ * verdicts[b] = 1 / 0 is what bgls_verify_multi_hae returns for set b alone (the exponents are hashed from set b's keys only).
+ * apk_out: NULL or n_sets G2 points, apk_out[b] = getAggregatePubKey(set b) = sum_i t_i pk_i, byte-equal to the single path's sum.
+ * gt_out: NULL or n_sets GT elements, e(-sig_b, g2) * e(H(m_b), apk_b) after the final exponentiation.
+ * Errors as bgls_verify_multi_sets: a non-canonical or off-curve key or signature, a degenerate point step or an exhausted hash
+ * ANYWHERE fails the whole call with the single call's code and leaves verdicts undefined; non-monotone offsets, NULL arguments, 2^30
+ * keys or more in all or 2^28 or more in one set (the XOF length is a uint32) are BGLS_ERR_ARG; n_sets == 0 returns 0.
+ * Returns the number of accepted sets (>= 0) or < 0. */
+int bgls_verify_multi_hae_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
+                               const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out);
+/* hashPubKeysToExponents (bgls/blsHAE.go:80-93) per set: t_out[16 key_off[b] ..] = the 16-byte exponents of set b, byte-equal to
+ * bgls_hae_exponents on that set alone.  Offsets and limits as bgls_verify_multi_hae_sets. */
+int bgls_hae_exponents_sets(int curve, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out);
+/* Sets with more than n keys have their BLAKE2Xb root computed on the host by the host-pointer entries (bgls_verify_multi_hae_sets,
+ * bgls_hae_exponents_sets); the others on the device, one lane per set.  Results do not depend on it.  Returns 0. */
+int bgls_set_hae_root_host_min(size_t n);
 /* getAggregatePubKey over device-resident inputs (bgls/blsHAE.go:74-77 = AggregatePoints(ScalePoints(points, w)),
  * curves/curve.go:73-121,190-214): d_out (affine bytes of the group) = sum_i w_i P_i, weights = n 16-byte big-endian
  * magnitudes.  Computed by the bucket method (k_msm.hip: a counting sort of the (point, window) pairs by digit, one
@@ -359,6 +376,11 @@ int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void
 int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
                                size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
                                uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_verify_multi_hae_sets with everything on the device, shaped as bgls_verify_multi_sets_dev (d_key_off read back and checked,
+ * every root on the device).  Same semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns. */
+int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
+                                   size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
+                                   uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream);
 /* bgls_bb_verify_batch with its inputs on the device (same layouts).  Same semantics and return value; synchronises `stream`
  * (NULL: the context's stream) before it returns. */
 int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms,
