@@ -23,26 +23,17 @@ size_t bgls_gt_size(int curve) { return 12 * bgls_fp_size(curve); }
 
 int bgls_verify_aggregate(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                           size_t n, int allow_duplicates) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!sig || !msg_off || (n && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_aggregate_t<CV>(sig, keys, msg_blob, msg_off, n, allow_duplicates));
 } BGLS_ABI_GUARD
 
-// offsets of a batch of instances: monotone from 0, below 2^30 pairs in all
-static int inst_off_ok(const uint64_t* inst_off, size_t n_inst) {
-  if (inst_off[0] != 0) return fail(BGLS_ERR_ARG, "inst_off must start at 0");
-  for (size_t b = 0; b < n_inst; ++b)
-    if (inst_off[b + 1] < inst_off[b]) return fail(BGLS_ERR_ARG, "inst_off not monotone");
-  if (inst_off[n_inst] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
-  return 0;
-}
-
 int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* msg_blob,
                                 const uint64_t* msg_off, int allow_duplicates, uint8_t* verdicts, uint8_t* gt_out) try {
-  if (n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_inst >= MAX_BATCH) return too_large();
   if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
   int rc;
-  if ((rc = inst_off_ok(inst_off, n_inst))) return rc;
+  if ((rc = offsets_ok("inst_off", inst_off, n_inst, OFF_FROM_ZERO | OFF_TOTAL))) return rc;
   if (n_inst == 0) return 0;
   if (!sigs || !verdicts || !msg_off || (inst_off[n_inst] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_aggregate_batch_t<CV>(sigs, keys, inst_off, n_inst, msg_blob, msg_off, allow_duplicates, verdicts, gt_out));
@@ -50,24 +41,24 @@ int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* k
 
 int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs,
                                     size_t msg_len, size_t msg_stride, int allow_duplicates, uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
-  if (n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_inst >= MAX_BATCH) return too_large();
   if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
   int rc;
-  if ((rc = inst_off_ok(inst_off, n_inst))) return rc;
+  if ((rc = offsets_ok("inst_off", inst_off, n_inst, OFF_FROM_ZERO | OFF_TOTAL))) return rc;
   if (n_inst == 0) return 0;
   if (!d_sigs || !verdicts || (inst_off[n_inst] && (!d_keys || (msg_len && !d_msgs)))) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_aggregate_batch_dev_t<CV>(d_sigs, d_keys, inst_off, n_inst, d_msgs, msg_len, msg_stride, allow_duplicates, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi(int curve, const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!sig || (n && !keys) || (msg_len && !msg)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_t<CV>(sig, keys, n, msg, msg_len));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
                             const uint64_t* msg_off, int allow_duplicates) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (!key_off || !msg_off || (n_sets && (!sigs || !msg_blob)) || (n_sets && key_off[n_sets] > key_off[0] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_batch_t<CV>(sigs, keys, key_off, n_sets, msg_blob, msg_off, allow_duplicates));
 } BGLS_ABI_GUARD
@@ -79,57 +70,44 @@ int bgls_aggregate_sets(int curve, int group, const uint8_t* pts, const uint64_t
 
 int bgls_verify_multi_batch_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
                                 const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (n_sets && (!d_sigs || !d_keys || !d_key_off || !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_batch_sub_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, allow_duplicates, stream, false));
 } BGLS_ABI_GUARD
 int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
                                        const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates, void* stream) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (n_sets && (!d_sigs || !d_keys || !d_key_off || !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_batch_sub_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, allow_duplicates, stream, true));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
                            const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (!key_off || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
-  for (size_t b = 0; b < n_sets; ++b) {
-    if (key_off[b + 1] < key_off[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
-    if (msg_off[b + 1] < msg_off[b]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  }
+  int rc;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, OFF_TOTAL))) return rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n_sets, 0))) return rc;
   if (n_sets == 0) return 0;
-  if (key_off[n_sets] - key_off[0] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
   if (!sigs || !verdicts || (msg_off[n_sets] && !msg_blob) || (key_off[n_sets] > key_off[0] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_sets_t<CV>(sigs, keys, key_off, n_sets, msg_blob, msg_off, verdicts, gt_out));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs,
                                size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (n_sets == 0) return 0;
   if (!d_sigs || !d_key_off || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
-// offsets of a batch of HAE sets: monotone, below 2^30 keys in all and 2^28 per set
-static int hae_sets_off_ok(const uint64_t* key_off, size_t n_sets) {
-  for (size_t b = 0; b < n_sets; ++b) {
-    if (key_off[b + 1] < key_off[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
-    if (key_off[b + 1] - key_off[b] >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (blsHAE.go:81)");
-  }
-  if (key_off[n_sets] - key_off[0] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
-  return 0;
-}
-
 int bgls_verify_multi_hae_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
                                const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (!key_off || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
-  for (size_t b = 0; b < n_sets; ++b)
-    if (msg_off[b + 1] < msg_off[b]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
   int rc;
-  if ((rc = hae_sets_off_ok(key_off, n_sets))) return rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n_sets, 0))) return rc;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, OFF_HAE | OFF_TOTAL))) return rc;
   if (n_sets == 0) return 0;
   if (!sigs || !verdicts || (msg_off[n_sets] && !msg_blob) || (key_off[n_sets] > key_off[0] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_hae_sets_t<CV>(sigs, keys, key_off, n_sets, msg_blob, msg_off, verdicts, apk_out, gt_out));
@@ -138,7 +116,7 @@ int bgls_verify_multi_hae_sets(int curve, const uint8_t* sigs, const uint8_t* ke
 int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
                                    const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out,
                                    void* stream) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (n_sets == 0) return 0;
   if (!d_sigs || !d_key_off || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_hae_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, apk_out, gt_out,
@@ -146,10 +124,10 @@ int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_
 } BGLS_ABI_GUARD
 
 int bgls_hae_exponents_sets(int curve, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out) try {
-  if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_sets >= MAX_BATCH) return too_large();
   if (!key_off) return fail(BGLS_ERR_ARG, "NULL argument");
   int rc;
-  if ((rc = hae_sets_off_ok(key_off, n_sets))) return rc;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, OFF_HAE | OFF_TOTAL))) return rc;
   if (n_sets == 0) return 0;
   if (key_off[n_sets] > key_off[0] && (!keys || !t_out)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, hae_exponents_sets_t<CV>(keys, key_off, n_sets, t_out));
@@ -162,7 +140,7 @@ int bgls_set_hae_root_host_min(size_t n) try {
 
 int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, uint8_t* verdicts,
                          uint8_t* gt_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (n == 0) return 0;
   if (!sigmas || !rs || !keys || !ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, bb_verify_t<CV>(sigmas, rs, keys, ms, n, verdicts, gt_out));
@@ -170,33 +148,33 @@ int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, co
 
 int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n, uint8_t* verdicts,
                              uint8_t* gt_out, void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (n == 0) return 0;
   if (!d_sigmas || !d_rs || !d_keys || !d_ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, bb_verify_dev_t<CV>(d_sigmas, d_rs, d_keys, d_ms, n, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
 int bgls_pairing_product(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!gt_out || (n && (!g1s || !g2s))) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, pairing_product_t<CV>(g1s, g2s, n, gt_out));
 } BGLS_ABI_GUARD
 
 int bgls_hash_to_g1(int curve, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint8_t* g1_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (n && (!msg_off || !g1_out)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, hash_to_g1_t<CV>(msg_blob, msg_off, n, g1_out));
 } BGLS_ABI_GUARD
 
 int bgls_aggregate_points(int curve, int group, const uint8_t* pts, size_t n, uint8_t* out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || !out || (n && !pts)) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   DISPATCH(curve, aggregate_points_t<CV>(group, pts, n, out));
 } BGLS_ABI_GUARD
 
 int bgls_scale_points(int curve, int group, const uint8_t* pts, const uint8_t* scalars, const uint8_t* signs, size_t n,
                       uint8_t* out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!pts || !scalars || !out))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   DISPATCH(curve, scale_points_t<CV>(group, pts, scalars, signs, n, out));
 } BGLS_ABI_GUARD
@@ -217,7 +195,7 @@ int bgls_point_check(int curve, int group, const uint8_t* a) try {
 } BGLS_ABI_GUARD
 
 int bgls_check_points(int curve, int group, const uint8_t* pts, size_t n, uint8_t* ok_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!pts || !ok_out))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   DISPATCH(curve, check_points_t<CV>(group, pts, n, ok_out));
 } BGLS_ABI_GUARD
@@ -229,7 +207,7 @@ int bgls_select_device(int device) try {
 } BGLS_ABI_GUARD
 
 int bgls_keys_upload(int curve, const uint8_t* keys, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* handle_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!handle_out || (n && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   if (n_devices < 1 || n_devices > NCTX) return fail(BGLS_ERR_ARG, "n_devices out of range (1..16)");
   int dflt = cur_device();
@@ -261,7 +239,7 @@ int bgls_keys_info(bgls_keys_t handle, int* curve, size_t* n, int* n_devices) tr
 
 int bgls_verify_aggregate_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n,
                             int allow_duplicates) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   auto ks = keyset(handle);
   if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
   if (!sig || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
@@ -270,7 +248,7 @@ int bgls_verify_aggregate_h(bgls_keys_t handle, const uint8_t* sig, const uint8_
 
 int bgls_verify_aggregate_h_gt(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n,
                                int allow_duplicates, uint8_t* gt_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   auto ks = keyset(handle);
   if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
   if (!sig || !msg_off || !gt_out) return fail(BGLS_ERR_ARG, "NULL argument");
@@ -283,7 +261,7 @@ int bgls_rccl_available(void) try { return rccl().ok ? 1 : 0; } BGLS_ABI_GUARD
 // on several contexts: the handle's resident arrays are read-only)
 int bgls_miller_product_keys_dev(bgls_keys_t handle, const void* d_sig, const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n,
                                  int check_duplicates, void* d_partial_out, void* d_flags, void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   auto ks = keyset(handle);
   if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
   if (ks->shards.size() != 1) return fail(BGLS_ERR_ARG, "device entry point: the key set must live on one device");
@@ -360,7 +338,7 @@ int bgls_verify_multi_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* m
 
 int bgls_verify_aggregate_multi(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                                 size_t n, int allow_duplicates, const int* devices, int n_devices) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   bgls_keys_t h;
   // host keys arrive unvalidated here (no Point construction in between): the upload checks the order-r subgroup as the
   // reference's constructors do, so a small-order twist point is an encoding error, not an unspecified verdict
@@ -375,7 +353,7 @@ int bgls_verify_aggregate_multi(int curve, const uint8_t* sig, const uint8_t* ke
 
 int bgls_verify_multi_multi(int curve, const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len,
                             const int* devices, int n_devices) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   bgls_keys_t h;
   int rc = bgls_keys_upload(curve, keys, n, devices, n_devices, BGLS_KEYS_CHECK, &h);
   if (rc) return rc;
@@ -494,11 +472,11 @@ int bgls_selftest_exception_barrier(int kind) try {
 
 int bgls_probe_mad_peak(double* mac_per_s) try {
   if (!mac_per_s) return fail(BGLS_ERR_ARG, "NULL argument");
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void* sink;
   if ((rc = c.get(WS_OUT, 16, &sink))) return rc;
   const int iters = 4096, blocks = 256 * 8, threads = 256;
@@ -526,7 +504,7 @@ int bgls_probe_mad_peak(double* mac_per_s) try {
 int bgls_miller_product_dev(int curve, const void* d_sig, const void* d_keys, const void* d_msgs, size_t msg_len,
                             size_t msg_stride, size_t n, int check_duplicates, void* d_partial_out, void* d_flags,
                             void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!d_partial_out || !d_flags || (n && (!d_keys || (!d_msgs && msg_len)))) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, miller_product_dev_t<CV>(d_sig, d_keys, d_msgs, msg_len, msg_stride, n, check_duplicates, d_partial_out,
                                            d_flags, stream));
@@ -558,7 +536,7 @@ int bgls_set_msm_min(size_t n) try {
 int bgls_weighted_sum_dev(int curve, int group, const void* d_pts, const void* d_w16, size_t n, void* d_out, void* stream) try {
   if (group != BGLS_G1 && group != BGLS_G2) return fail(BGLS_ERR_ARG, "bad group");
   if (!d_out || (n && (!d_pts || !d_w16))) return fail(BGLS_ERR_ARG, "NULL argument");
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   DISPATCH(curve, weighted_sum_dev_t<CV>(group, d_pts, d_w16, n, d_out, stream));
 } BGLS_ABI_GUARD
 
@@ -580,7 +558,7 @@ int bgls_final_verify_collect(int curve) try {
 } BGLS_ABI_GUARD
 
 int bgls_duplicate_scan_dev(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_flags, void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!d_flags || (n && !d_msgs && msg_len)) return fail(BGLS_ERR_ARG, "NULL argument");
   if (n >= (1ull << 30)) return fail(BGLS_ERR_ARG, "too many messages for one scan");
   return duplicate_scan_dev(d_msgs, msg_len, msg_stride, n, d_flags, stream);
@@ -588,7 +566,7 @@ int bgls_duplicate_scan_dev(const void* d_msgs, size_t msg_len, size_t msg_strid
 
 int bgls_duplicate_scan_bucket_dev(const void* d_recs, size_t rec_len, size_t rec_stride, size_t n, unsigned bucket, unsigned n_buckets, void* d_flags,
                                    void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!d_flags || (n && !d_recs && rec_len)) return fail(BGLS_ERR_ARG, "NULL argument");
   if (n_buckets < 1 || n_buckets > 256 || bucket >= n_buckets) return fail(BGLS_ERR_ARG, "bucket out of range (bucket < n_buckets <= 256)");
   return duplicate_scan_dev(d_recs, rec_len, rec_stride, n, d_flags, stream, bucket, n_buckets);
@@ -603,22 +581,22 @@ int bgls_digest_pack_dev(const void* d_digests16, size_t n, unsigned n_buckets, 
 } BGLS_ABI_GUARD
 
 int bgls_duplicate_scan_packed_dev(const void* d_recs16, size_t n_slots, unsigned bucket, unsigned n_buckets, void* d_flags, void* stream) try {
-  if (n_slots >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n_slots >= MAX_BATCH) return too_large();
   if (!d_flags || (n_slots && !d_recs16)) return fail(BGLS_ERR_ARG, "NULL argument");
   if (n_buckets < 2 || n_buckets > 256 || bucket >= n_buckets) return fail(BGLS_ERR_ARG, "bucket out of range (bucket < n_buckets, 2 <= n_buckets <= 256)");
   return duplicate_scan_dev(d_recs16, 16, 16, n_slots, d_flags, stream, bucket, n_buckets, true);
 } BGLS_ABI_GUARD
 
 int bgls_message_digests_dev(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_out16, void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (n && (!d_out16 || (!d_msgs && msg_len))) return fail(BGLS_ERR_ARG, "NULL argument");
   if (((uintptr_t)d_out16 & 15) != 0) return fail(BGLS_ERR_ARG, "digest buffer must be 16-byte aligned");
   if (n == 0) return 0;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
   kl::msg_digest(st, mv, n, (uint8_t*)d_out16);
   HIPCHK(hipGetLastError());
@@ -631,54 +609,54 @@ int bgls_final_verify_dev(int curve, const void* d_partials, size_t count, const
 } BGLS_ABI_GUARD
 
 int bgls_aggregate_points_dev(int curve, int group, const void* d_pts, size_t n, void* d_out, void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || !d_out || (n && !d_pts)) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   DISPATCH(curve, aggregate_points_dev_t<CV>(group, d_pts, n, d_out, stream));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_dev(int curve, const void* d_sig, const void* d_keys, size_t n, const void* d_msg, size_t msg_len,
                           void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!d_sig || (n && !d_keys) || (msg_len && !d_msg)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_dev_entry_t<CV>(d_sig, d_keys, n, d_msg, msg_len, stream));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_submit_dev(int curve, const void* d_sig, const void* d_keys, size_t n, const void* d_msg, size_t msg_len,
                                  void* stream) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!d_sig || (n && !d_keys) || (msg_len && !d_msg)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_dev_entry_t<CV>(d_sig, d_keys, n, d_msg, msg_len, stream, true));
 } BGLS_ABI_GUARD
 
 /* ---- hashed aggregation exponents (bgls/blsHAE.go) and multiplicities (bgls/blsKosk.go:137-150) ---- */
 int bgls_hae_exponents(int curve, const uint8_t* keys, size_t n, uint8_t* t_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (n && (!keys || !t_out)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, hae_exponents_t<CV>(keys, n, t_out));
 } BGLS_ABI_GUARD
 
 int bgls_aggregate_signatures_hae(int curve, const uint8_t* sigs, const uint8_t* keys, size_t n, uint8_t* out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!out || (n && (!sigs || !keys))) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, aggregate_signatures_hae_t<CV>(sigs, keys, n, out));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_hae(int curve, const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!sig || (n && !keys) || (msg_len && !msg)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_multi_weighted_t<CV>(sig, keys, nullptr, n, msg, msg_len));
 } BGLS_ABI_GUARD
 
 int bgls_verify_aggregate_hae(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                               size_t n) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!sig || !msg_off || (n && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, verify_aggregate_hae_t<CV>(sig, keys, msg_blob, msg_off, n));
 } BGLS_ABI_GUARD
 
 int bgls_verify_multi_multiplicity(int curve, const uint8_t* sig, const uint8_t* keys, const int64_t* multiplicity, size_t n,
                                    const uint8_t* msg, size_t msg_len) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!sig || (n && !keys) || (msg_len && !msg)) return fail(BGLS_ERR_ARG, "NULL argument");
   if (!multiplicity) DISPATCH(curve, verify_multi_t<CV>(sig, keys, n, msg, msg_len));
   DISPATCH(curve, verify_multi_weighted_t<CV>(sig, keys, multiplicity, n, msg, msg_len));
@@ -686,26 +664,26 @@ int bgls_verify_multi_multiplicity(int curve, const uint8_t* sig, const uint8_t*
 
 /* ---- compressed wire formats (alt-bn128; curves/altbn128.go:81-89,203-221,296-376) ---- */
 int bgls_compress_points(int curve, int group, const uint8_t* pts, size_t n, uint8_t* out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!pts || !out))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   return wire_points(curve, group, true, pts, n, out, nullptr);
 } BGLS_ABI_GUARD
 
 int bgls_decompress_points(int curve, int group, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!in || !out || !ok))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   return wire_points(curve, group, false, in, n, out, ok);
 } BGLS_ABI_GUARD
 
 /* ---- batch key generation / signing (bgls/bgls.go:40-56) ---- */
 int bgls_scale_generator(int curve, int group, const uint8_t* scalars, size_t n, uint8_t* out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!scalars || !out))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   DISPATCH(curve, scale_generator_t<CV>(group, scalars, n, out));
 } BGLS_ABI_GUARD
 
 int bgls_sign_batch(int curve, const uint8_t* sks, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint8_t* sigs_out) try {
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if (!msg_off || (n && (!sks || !sigs_out))) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(curve, sign_batch_t<CV>(sks, msg_blob, msg_off, n, sigs_out));
 } BGLS_ABI_GUARD

@@ -15,6 +15,9 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) noexcept {
   try { g_err = buf; } catch (...) {}      // the message is best effort, the code is the contract
   return code;
 }
+// the two refusals that many calls share
+int too_large() noexcept { return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)"); }
+int in_flight() noexcept { return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)"); }
 
 // The exception barrier of the C ABI ("no exceptions, no abort()": include/bgls_hip.h; the reference never panics and returns
 // (nil, false): curves/curve.go:15-22).  Every extern "C" body below is a function-try-block ending in BGLS_ABI_GUARD: host
@@ -47,6 +50,16 @@ struct SideJoin {
     if (armed) (void)hipStreamSynchronize(side);
   }
 };
+// Error-path guard of a call that returns results to host memory: an error return between the first launch and the call's own
+// synchronise leaves launches, and copies out of host staging vectors (Ctx::stage_tab), in flight.  Armed from the start, disarmed after
+// that synchronise; an error return in between drains the stream.
+struct Drain {
+  hipStream_t st;
+  bool armed = true;
+  ~Drain() {
+    if (armed) (void)hipStreamSynchronize(st);
+  }
+};
 
 #define HIPCHK(expr)                                         \
   do {                                                       \
@@ -61,6 +74,30 @@ constexpr size_t MAX_BATCH = (size_t)1 << 30;
 constexpr size_t HAE_MAX_SET = (size_t)1 << 28;
 // batches up to this many pairings take the latency form of the Miller loop (one block per pairing, k_miller_lat)
 constexpr size_t LAT_MAX = 128;
+
+// The rules of a table of count + 1 host offsets, stated once (`name` is the table's name in the messages): from 0 where OFF_FROM_ZERO
+// asks for it, monotone, no segment above max_seg, under OFF_HAE no segment of 2^28 entries or more, under OFF_TOTAL fewer than 2^30
+// entries in all.  *largest (nullable): the largest segment.
+enum { OFF_FROM_ZERO = 1, OFF_HAE = 2, OFF_TOTAL = 4 };
+int offsets_ok(const char* name, const uint64_t* off, size_t count, unsigned rules, size_t max_seg = SIZE_MAX, size_t* largest = nullptr) {
+  auto named = [name](const char* what) {
+    char msg[64];
+    snprintf(msg, sizeof msg, "%s %s", name, what);
+    return fail(BGLS_ERR_ARG, msg);
+  };
+  size_t top = 0;
+  if ((rules & OFF_FROM_ZERO) && off[0] != 0) return named("must start at 0");
+  for (size_t b = 0; b < count; ++b) {
+    if (off[b + 1] < off[b]) return named("not monotone");
+    const size_t seg = off[b + 1] - off[b];
+    if (seg > max_seg) return fail(BGLS_ERR_ARG, "a set is larger than max_set");
+    if ((rules & OFF_HAE) && seg >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (blsHAE.go:81)");
+    if (seg > top) top = seg;
+  }
+  if ((rules & OFF_TOTAL) && count && off[count] - off[0] >= MAX_BATCH) return too_large();
+  if (largest) *largest = top;
+  return 0;
+}
 
 // workspace slots
 enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
@@ -132,6 +169,13 @@ struct Ctx {
     *out = ws[slot].first;
     return 0;
   }
+  // slot sized for bytes (+ spare), filled with `bytes` of host memory by a copy on st (no copy of nothing)
+  int put(hipStream_t st, int slot, const void* src, size_t bytes, void** out, size_t spare = 0) {
+    int rc;
+    if ((rc = get(slot, bytes + spare, out))) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(*out, src, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+  }
 };
 
 // Contexts: each owns a stream, its workspaces and its stage timers.  A host thread works on context (device, index) =
@@ -165,6 +209,16 @@ Ctx* ctx_pool() {
 int cur_device() { return g_dev >= 0 ? g_dev : g_default_device.load(); }
 Ctx& ctx_of(int device, int index) { return ctx_pool()[(size_t)device * NCTX + index]; }
 Ctx& ctx() { return ctx_of(cur_device(), g_sel); }
+
+// The opening of a call body: the calling thread's context with its lock held for the body, the device made current, and the stream
+// the call works on -- the caller's where it gave one, else the context's.  rc != 0: Ctx::enter's code, to be returned before anything else.
+struct Call {
+  Ctx& c;
+  std::lock_guard<std::mutex> lk;
+  const int rc;
+  const hipStream_t st;
+  explicit Call(void* stream = nullptr) : c(ctx()), lk(c.mu), rc(c.enter()), st(stream ? (hipStream_t)stream : c.stream) {}
+};
 
 // Per-device tables built once: the fixed-argument line coefficients of the generator g2 (k_gen_lines), one per curve,
 // and the window multiples d 2^(8j) g of both generators for batch key generation (k_fb_build).
@@ -332,7 +386,7 @@ struct Engine {
   // table is sized for ALL of them (it cannot fill up: the scan is exact and probes without a bound), the bucket filter only skips the padding.
   static int dup_scan(Ctx& c, hipStream_t st, MsgView mv, size_t n, uint32_t* d_flags, uint32_t bucket = 0, uint32_t n_buckets = 1, bool packed = false) {
     if (n < 2) return 0;
-    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH) return too_large();
     const size_t share = n_buckets > 1 && !packed ? 2 * (n / n_buckets) + 4096 : n;
     size_t cap = 1;
     while (cap < 2 * (share < n ? share : n)) cap <<= 1;
@@ -351,7 +405,7 @@ struct Engine {
   // d_w16 != nullptr: pair i is (w_i H(m_i), pk_i) with 16-byte big-endian weights (hashed aggregation exponents).
   static int miller_product(Ctx& c, hipStream_t st, const uint8_t* d_sig, const uint8_t* d_keys, MsgView mv, size_t n,
                             int check_dups, uint8_t* d_partial, uint32_t* d_flags, const uint8_t* d_w16 = nullptr) {
-    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH) return too_large();
     const bool raw = C::CURVE_ID == 1 && n > 0;           // BLS12-381: uncleared hash points, cofactor applied once in GT (any batch size:
                                                           // clearing it per message is a 126-bit scalar multiplication on a lone lane, 4.8 ms)
     void* g1s;
@@ -394,7 +448,7 @@ struct Engine {
   // line ratios.  BLS12-381 hash points stay uncleared as on the unprepared path: the cofactor is applied once in GT.
   static int miller_product_prepared(Ctx& c, hipStream_t st, const uint8_t* d_sig, const uint32_t* d_prep, const uint8_t* d_kinf, size_t n_pad, int ng,
                                      MsgView mv, size_t n, uint8_t* d_partial, uint32_t* d_flags) {
-    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH) return too_large();
     void *g1s, *ptab, *pa, *pb;
     int rc;
     if ((rc = c.get(WS_G1S, (n + 2) * sizeof(Aff<G1F>), &g1s))) return rc;
@@ -439,7 +493,7 @@ struct Engine {
   static int miller_product_batch(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
                                   int check_dups, uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags) {
     const size_t n = inst_off[n_inst];
-    if (n >= MAX_BATCH || n_inst >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH || n_inst >= MAX_BATCH) return too_large();
     constexpr bool raw = C::CURVE_ID == 1;                // BLS12-381: uncleared hash points, the cofactor applied per instance in the epilogue
     // host tables, uploaded in one copy: inst_off, pad_off, then the segment tables of the reduce passes ({start, count} words)
     std::vector<uint64_t>& tab = c.stage_tab;
@@ -447,7 +501,7 @@ struct Engine {
     for (size_t b = 0; b <= n_inst; ++b) tab[b] = inst_off[b];
     for (size_t b = 0; b < n_inst; ++b) tab[n_inst + 2 + b] = tab[n_inst + 1 + b] + (inst_off[b + 1] - inst_off[b] + 5) / 6 * 6;
     const size_t n_pad = tab[2 * n_inst + 1];
-    if (n_pad >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n_pad >= MAX_BATCH) return too_large();
     const size_t nb = (n_pad + 59) / 60, groups = nb * 10;
     // reduce passes, planned on the host: segment b holds cnt[b] partials from pos[b]; a pass leaves ceil(cnt / R) of them (one for an
     // empty segment), until every instance has exactly one.  Kernel per pass as in Engine::reduce: k_reduce_fx (R = 10) once at most
@@ -554,6 +608,28 @@ struct Engine {
     return 0;
   }
 
+  // The k_miller_sets launch sequence (ST_MILLER) of Engine::miller_multi_sets and Engine::miller_bb: m accumulators, accumulator b over the
+  // pair (g1s[b], d_q[b] as wire bytes) and, where sigs[b] is not at infinity, (sigs[b], g2) on the generator lines gl.  BLS12-381: the
+  // w-basis values to rest (6 Fp2 each, for the caller's epilogue); alt-bn128: GT bytes to d_partials.
+  static int miller_sets(Ctx& c, hipStream_t st, const Aff<G1F>* g1s, const uint8_t* d_q, const Aff<G1F>* sigs, const LineCoeffs<C>* gl, size_t m, Fp2<C>* rest,
+                         uint8_t* d_partials, uint32_t* d_flags) {
+    constexpr bool bls = C::CURVE_ID == 1;
+    constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
+    const size_t spb = kl::miller_sets_per_block<C>(), nb = (m + spb - 1) / spb;
+    void* park;
+    int rc;
+    if ((rc = c.get(WS_QP, kl::miller_sets_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
+    Scope sc(c, st, ST_MILLER);
+    for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
+      const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
+      const size_t s0 = blk0 * spb;
+      kl::miller_sets<C>(st, (unsigned)nblocks, g1s + s0, d_q + s0 * G2B, sigs + s0, gl, m - s0, bls ? rest + s0 * 6 : nullptr,
+                         bls ? nullptr : d_partials + s0 * GTB, d_flags, (uint32_t*)park);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+
   // A batch of n_sets independent multi-signature verifications (bgls_verify_multi_sets): set b is the signature d_sigs[b] (wire
   // bytes), the key sum d_apks[b] (wire bytes, Engine::sum_sets) and message b of mv.  Every stage runs once for the batch: one
   // hashing pass, the parse of the -sigma_b, one k_miller_sets launch sequence (one accumulator per set: the hash pair and, on
@@ -561,15 +637,12 @@ struct Engine {
   // single path's order for uncleared hash points).  Writes n_sets GT partials (bytes, no final exponentiation) to d_partials.
   static int miller_multi_sets(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_apks, MsgView mv, size_t n_sets, uint8_t* d_partials,
                                uint32_t* d_flags) {
-    if (n_sets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n_sets >= MAX_BATCH) return too_large();
     constexpr bool bls = C::CURVE_ID == 1;                // uncleared hash points, the cofactor applied per set in the epilogue
-    void *g1s, *sigs, *park, *rest = nullptr, *epi = nullptr;
+    void *g1s, *sigs, *rest = nullptr, *epi = nullptr;
     int rc;
-    constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
-    const size_t spb = kl::miller_sets_per_block<C>(), nb = (n_sets + spb - 1) / spb;
     if ((rc = c.get(WS_G1S, (n_sets + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
     if ((rc = c.get(WS_BATCH_SIGS, (n_sets + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
-    if ((rc = c.get(WS_QP, kl::miller_sets_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
     if (bls) {
       if ((rc = c.get(WS_F_A, (n_sets + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
       if ((rc = c.get(WS_BATCH_EPI, (n_sets + 1) * 12 * sizeof(Fp2<C>), &epi))) return rc;
@@ -581,16 +654,7 @@ struct Engine {
       if ((rc = hash_to_g1(c, st, mv, n_sets, (Aff<G1F>*)g1s, d_flags, bls))) return rc;
     }
     kl::g1_parse<C>(st, d_sigs, n_sets, 1, (Aff<G1F>*)sigs, d_flags);                         // -sigma_b
-    {
-      Scope sc(c, st, ST_MILLER);
-      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
-        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
-        const size_t s0 = blk0 * spb;
-        kl::miller_sets<C>(st, (unsigned)nblocks, (const Aff<G1F>*)g1s + s0, d_apks + s0 * G2B, (const Aff<G1F>*)sigs + s0, gl, n_sets - s0,
-                           bls ? (Fp2<C>*)rest + s0 * 6 : nullptr, bls ? nullptr : d_partials + s0 * GTB, d_flags, (uint32_t*)park);
-      }
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = miller_sets(c, st, (const Aff<G1F>*)g1s, d_apks, (const Aff<G1F>*)sigs, gl, n_sets, (Fp2<C>*)rest, d_partials, d_flags))) return rc;
     if (bls) {
       Scope sc(c, st, ST_EPI);
       kl::epiloguex_seg<C>(st, n_sets, (const Fp2<C>*)rest, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
@@ -607,18 +671,15 @@ struct Engine {
   // final exponentiation) to d_partials.
   static int miller_bb(Ctx& c, hipStream_t st, const uint8_t* d_sigmas, const uint8_t* d_rs, const uint8_t* d_keys, const uint8_t* d_ms, size_t n,
                        uint8_t* d_partials, uint32_t* d_flags) {
-    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH) return too_large();
     constexpr bool bls = C::CURVE_ID == 1;
     const size_t m = n + 1;                               // the items and the reference pair
-    void *g1s, *qs, *nosig, *park, *rest = nullptr;
+    void *g1s, *qs, *nosig, *rest = nullptr;
     const void* fb;
     int rc;
-    constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
-    const size_t spb = kl::miller_sets_per_block<C>(), nb = (m + spb - 1) / spb;
     if ((rc = c.get(WS_G1S, (m + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
     if ((rc = c.get(WS_SEG_KEYS, (m + 1) * G2B, &qs))) return rc;
     if ((rc = c.get(WS_BATCH_SIGS, (m + 1) * sizeof(Aff<G1F>), &nosig))) return rc;
-    if ((rc = c.get(WS_QP, kl::miller_sets_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
     if (bls && (rc = c.get(WS_F_A, (m + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
     const LineCoeffs<C>* gl = nullptr;
     if ((rc = gen_lines(c, &gl))) return rc;
@@ -629,16 +690,7 @@ struct Engine {
       kl::bb_keys<C>(st, d_keys, d_rs, d_ms, fb, n, (uint8_t*)qs, (Aff<G1F>*)g1s, bls ? nullptr : (Aff<G1F>*)nosig, d_flags);
       HIPCHK(hipGetLastError());
     }
-    {
-      Scope sc(c, st, ST_MILLER);
-      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
-        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
-        const size_t s0 = blk0 * spb;
-        kl::miller_sets<C>(st, (unsigned)nblocks, (const Aff<G1F>*)g1s + s0, (const uint8_t*)qs + s0 * G2B, (const Aff<G1F>*)nosig + s0, gl, m - s0,
-                           bls ? (Fp2<C>*)rest + s0 * 6 : nullptr, bls ? nullptr : d_partials + s0 * GTB, d_flags, (uint32_t*)park);
-      }
-      HIPCHK(hipGetLastError());
-    }
+    if ((rc = miller_sets(c, st, (const Aff<G1F>*)g1s, (const uint8_t*)qs, (const Aff<G1F>*)nosig, gl, m, (Fp2<C>*)rest, d_partials, d_flags))) return rc;
     if (bls) {
       Scope sc(c, st, ST_EPI);
       kl::bb_w_bytes<C>(st, (const Fp2<C>*)rest, m, d_partials);
@@ -650,7 +702,7 @@ struct Engine {
   // H(m_i) as affine Montgomery points.  raw (BLS12-381 only): points before cofactor clearing, for the cofactor-in-GT
   // verification path (DESIGN.md section 3).
   static int hash_to_g1(Ctx& c, hipStream_t st, MsgView mv, size_t n, Aff<G1F>* out, uint32_t* d_flags, bool raw = false) {
-    if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+    if (n >= MAX_BATCH) return too_large();
     int rc;
     void *lists = nullptr, *cnts = nullptr;
     if constexpr (C::CURVE_ID == 0) {
@@ -869,7 +921,7 @@ struct Engine {
                              uint8_t* h_gt_out) {
     void *tmp, *fl;
     int rc;
-    if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
+    if (c.res_pending) return in_flight();
     if ((rc = c.get(WS_TMP, GTB + 16, &tmp))) return rc;
     if ((rc = c.get(WS_OUT, 16, &fl))) return rc;
     uint8_t* d_gt = (uint8_t*)tmp;

@@ -271,8 +271,7 @@ template <class C>
 int verify_aggregate_h_t(KeySet& ks, const uint8_t* sig, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups, uint8_t* gt_out) {
   typedef Engine<C> E;
   if (n != ks.n) return fail(BGLS_ERR_ARG, "message count differs from the key set's size");
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
+  if (int bad = offsets_ok("msg_off", off, n, 0)) return bad;
   std::lock_guard<std::mutex> lk_set(ks.mu);
   const size_t REC = E::GTB + REC_PAD;
   const int S = (int)ks.shards.size();

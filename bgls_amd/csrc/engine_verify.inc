@@ -8,6 +8,42 @@ int flags_to_rc(uint32_t f) {
   return 0;
 }
 
+// The close of a call that answers with its flag word: `bytes` of result from d_src to dst where there are any, the word itself, the stream
+// drained, the stage timers collected where the call does that, and the word's meaning as the return code.
+int read_flags(Ctx& c, hipStream_t st, const void* d_flags, bool collect, void* dst = nullptr, const void* d_src = nullptr, size_t bytes = 0) {
+  uint32_t f = 0;
+  if (bytes) HIPCHK(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (collect) c.collect();
+  return flags_to_rc(f);
+}
+
+// The messages of a host-pointer call on the device: the n + 1 offsets, checked here and before anything of the call is enqueued, to
+// WS_IN_D, the blob to WS_IN_C.
+int upload_msgs(Ctx& c, hipStream_t st, const uint8_t* blob, const uint64_t* off, size_t n, MsgView* mv) {
+  int rc;
+  void *d_blob, *d_off;
+  if ((rc = offsets_ok("msg_off", off, n, 0))) return rc;
+  if ((rc = c.put(st, WS_IN_C, blob, n ? off[n] : 0, &d_blob))) return rc;
+  if ((rc = c.put(st, WS_IN_D, off, (n + 1) * 8, &d_off))) return rc;
+  *mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  return 0;
+}
+
+// The points of the sets of a host-pointer call on the device (PB bytes each): points off[0] .. off[n_sets] to *d_pts (WS_IN_B), the offsets
+// relative to off[0] to *d_off (WS_SEG_OFF) and to rel.  rel is the source of an asynchronous copy: the caller keeps it until it has
+// synchronised the stream.  Nothing of off is read when n_sets == 0.
+int upload_key_sets(Ctx& c, hipStream_t st, size_t PB, const uint8_t* pts, const uint64_t* off, size_t n_sets, void** d_pts, void** d_off,
+                std::vector<uint64_t>& rel) {
+  const size_t k0 = n_sets ? off[0] : 0;
+  int rc;
+  rel.assign(n_sets + 1, 0);
+  for (size_t i = 1; i <= n_sets; ++i) rel[i] = off[i] - k0;
+  if ((rc = c.put(st, WS_IN_B, rel[n_sets] ? pts + k0 * PB : nullptr, rel[n_sets] * PB, d_pts, PB))) return rc;
+  return c.put(st, WS_SEG_OFF, rel.data(), (n_sets + 1) * 8, d_off);
+}
+
 #define DISPATCH(curve, CALL)                                    \
   do {                                                           \
     if ((curve) == BGLS_CURVE_ALTBN128) {                        \
@@ -23,116 +59,117 @@ int flags_to_rc(uint32_t f) {
 template <class C>
 int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  const size_t blob_len = n ? off[n] : 0;
-  void *d_sig, *d_keys, *d_blob, *d_off, *d_flags, *d_part;
-  if ((rc = c.get(WS_IN_A, E::G1B, &d_sig))) return rc;
-  if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
+  MsgView mv;
+  void *d_sig, *d_keys, *d_flags, *d_part;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   if ((rc = c.get(WS_PART, E::GTB, &d_part))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sig, sig, E::G1B, hipMemcpyHostToDevice, st));
-  if (n) HIPCHK(hipMemcpyAsync(d_keys, keys, n * E::G2B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
   if ((rc = E::miller_product(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n, !allow_dups, (uint8_t*)d_part,
                               (uint32_t*)d_flags)))
     return rc;
   return E::finalize(c, st, (const uint8_t*)d_part, 1, 1, (const uint32_t*)d_flags, nullptr);
 }
 
-// n_inst independent VerifyAggregateSignature calls (bgls/bgls.go:94-119) in one set of launches (Engine::miller_product_batch), then one
-// final exponentiation per instance in ONE launch; verdicts[b] = 1 / 0, returns the number of accepted instances.  An encoding or hashing
-// failure anywhere fails the whole call with the single call's code.
-template <class C>
-int verify_aggregate_batch_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
-                               int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+// What a call with one verdict per item hands back, and the two things in which the Boneh-Boyen form differs from the others.
+struct BatchOut {
+  uint8_t* verdicts;                 // n bytes, 1 / 0
+  uint8_t* gt = nullptr;             // nullable: the n GT elements
+  uint8_t* apks = nullptr;           // nullable: the n key sums of a batch of sets, wire bytes, from d_apks
+  const uint8_t* d_apks = nullptr;
+  bool bb = false;                   // Boneh-Boyen: item n is the reference pair (g1, g2), verdict b = (GT element b == GT element n)
+};
+
+// The common tail of the calls with one verdict per item (aggregate instances, multi-signature sets with plain or hashed key sums,
+// Boneh-Boyen signatures): stage(d_part, d_iflags, d_flags) runs the call's own launches up to one GT partial per item at d_part (no
+// final exponentiation; per-item refusals in d_iflags, encoding and hashing failures in d_flags, all zeroed here), then one final
+// exponentiation per item in ONE launch.  out.verdicts[b] = 1 / 0, returns the number of accepted items.  An encoding or hashing failure
+// anywhere fails the whole call with the single call's code.
+template <class C, class Stage>
+int batch_verdicts_run(Ctx& c, hipStream_t st, size_t n, const BatchOut& out, Stage&& stage) {
   typedef Engine<C> E;
-  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
-  // words: n_inst per-instance duplicate flags, n_inst verdicts, the call's flag word
+  if (c.res_pending) return in_flight();
+  const size_t m = out.bb ? n + 1 : n;                    // items through the final exponentiation
+  // words: m per-item flags, m verdicts of the final exponentiation, (Boneh-Boyen: whose verdicts against one are unused, then m words for
+  // the n verdicts of the comparison,) the call's flag word -- right behind the n verdicts, so that one copy fetches both
+  const size_t n_words = (out.bb ? 3 : 2) * m + 1;
+  const bool dev_gt = out.gt || out.bb;
   void *d_res, *d_part;
   int rc;
-  if ((rc = c.get(WS_BATCH_RES, (2 * n_inst + 1) * 4, &d_res))) return rc;
-  if ((rc = c.get(WS_PART, n_inst * E::GTB * (gt_out ? 2 : 1), &d_part))) return rc;
+  if ((rc = c.get(WS_BATCH_RES, n_words * 4, &d_res))) return rc;
+  if ((rc = c.get(WS_PART, m * E::GTB * (dev_gt ? 2 : 1), &d_part))) return rc;
   uint32_t* d_iflags = (uint32_t*)d_res;
-  uint32_t* d_verdicts = d_iflags + n_inst;
-  uint32_t* d_flags = d_verdicts + n_inst;
-  uint8_t* d_gt = gt_out ? (uint8_t*)d_part + n_inst * E::GTB : nullptr;
-  // an error return below leaves launches and the copy of the host tables (Ctx::stage_tab) in flight: drain the stream first
-  struct Drain {
-    hipStream_t st;
-    bool armed = true;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(st);
-    }
-  } drain{st};
-  HIPCHK(hipMemsetAsync(d_res, 0, (2 * n_inst + 1) * 4, st));
-  if ((rc = E::miller_product_batch(c, st, d_sigs, d_keys, mv, inst_off, n_inst, !allow_dups, (uint8_t*)d_part, d_iflags, d_flags))) return rc;
+  uint32_t* d_fx = d_iflags + m;
+  uint32_t* d_verdicts = out.bb ? d_fx + m : d_fx;
+  uint32_t* d_flags = d_verdicts + n;
+  uint8_t* d_gt = dev_gt ? (uint8_t*)d_part + m * E::GTB : nullptr;
+  Drain drain{st};
+  HIPCHK(hipMemsetAsync(d_res, 0, n_words * 4, st));
+  if ((rc = stage((uint8_t*)d_part, d_iflags, d_flags))) return rc;
   {
     Scope sc(c, st, ST_FINAL);
-    kl::finalx_batch<C>(st, (const uint8_t*)d_part, n_inst, d_gt, d_verdicts, d_iflags, d_flags);
+    kl::finalx_batch<C>(st, (const uint8_t*)d_part, m, d_gt, d_fx, d_iflags, d_flags);
+    if (out.bb) kl::bb_verdicts<C>(st, d_gt, n, d_verdicts);
   }
   HIPCHK(hipGetLastError());
-  std::vector<uint32_t> words(n_inst + 1);
-  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n_inst + 1) * 4, hipMemcpyDeviceToHost, st));
-  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n_inst * E::GTB, hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> words(n + 1);
+  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n + 1) * 4, hipMemcpyDeviceToHost, st));
+  if (out.gt) HIPCHK(hipMemcpyAsync(out.gt, d_gt, n * E::GTB, hipMemcpyDeviceToHost, st));
+  if (out.apks) HIPCHK(hipMemcpyAsync(out.apks, out.d_apks, n * E::G2B, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   drain.armed = false;
   c.collect();
-  if ((rc = flags_to_rc(words[n_inst]))) return rc;
+  if ((rc = flags_to_rc(words[n]))) return rc;
   int accepted = 0;
-  for (size_t b = 0; b < n_inst; ++b) {
-    verdicts[b] = words[b] ? 1 : 0;
+  for (size_t b = 0; b < n; ++b) {
+    out.verdicts[b] = words[b] ? 1 : 0;
     accepted += words[b] ? 1 : 0;
   }
   return accepted;
+}
+
+// n_inst independent VerifyAggregateSignature calls (bgls/bgls.go:94-119) in one set of launches (Engine::miller_product_batch, which sets
+// d_iflags[b] for a duplicate message within instance b), then batch_verdicts_run's tail.
+template <class C>
+int verify_aggregate_batch_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
+                               int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+  return batch_verdicts_run<C>(c, st, n_inst, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t* d_iflags, uint32_t* d_flags) {
+    return Engine<C>::miller_product_batch(c, st, d_sigs, d_keys, mv, inst_off, n_inst, !allow_dups, d_part, d_iflags, d_flags);
+  });
 }
 
 template <class C>
 int verify_aggregate_batch_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* blob, const uint64_t* off,
                              int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   const size_t n = inst_off[n_inst];
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  const size_t blob_len = n ? off[n] : 0;
-  void *d_sigs, *d_keys, *d_blob, *d_off;
-  if ((rc = c.get(WS_IN_A, n_inst * E::G1B, &d_sigs))) return rc;
-  if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_inst * E::G1B, hipMemcpyHostToDevice, st));
-  if (n) HIPCHK(hipMemcpyAsync(d_keys, keys, n * E::G2B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  MsgView mv;
+  void *d_sigs, *d_keys;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, n_inst * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
   return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
 }
 
 template <class C>
 int verify_aggregate_batch_dev_t(const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs, size_t msg_len,
                                  size_t msg_stride, int allow_dups, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  Call k(stream);
+  if (k.rc) return k.rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
+  return verify_aggregate_batch_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
 }
 
 template <class C>
@@ -141,7 +178,7 @@ int verify_multi_dev_t(Ctx& c, hipStream_t st, const uint8_t* d_sig, const uint8
   typedef Engine<C> E;
   int rc;
   void *d_flags, *d_g2s, *d_g1s, *d_part;
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   if ((rc = c.get(WS_TMP2, 2 * E::G2B, &d_g2s))) return rc;
   if ((rc = c.get(WS_G1S, 4 * sizeof(Aff<F1<C>>), &d_g1s))) return rc;
@@ -188,7 +225,7 @@ int verify_multi_batch_dev_t(Ctx& c, hipStream_t st, const uint8_t* d_sigs, cons
   typedef Engine<C> E;
   int rc;
   void *d_flags, *d_akeys, *d_sig, *d_part;
-  if (nsets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (nsets >= MAX_BATCH) return too_large();
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   if ((rc = c.get(WS_SEG_KEYS, (nsets + 1) * E::G2B, &d_akeys))) return rc;
   if ((rc = c.get(WS_TMP2, 2 * E::G2B, &d_sig))) return rc;
@@ -206,35 +243,20 @@ template <class C>
 int verify_multi_batch_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t nsets, const uint8_t* blob, const uint64_t* off,
                          int allow_dups) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   size_t max_set = 0;
-  for (size_t i = 0; i < nsets; ++i) {
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-    if (key_off[i + 1] < key_off[i]) return fail(BGLS_ERR_ARG, "key_off not monotone");
-    if (key_off[i + 1] - key_off[i] > max_set) max_set = key_off[i + 1] - key_off[i];
-  }
-  const size_t nkeys = nsets ? key_off[nsets] - key_off[0] : 0, k0 = nsets ? key_off[0] : 0;
-  if (nkeys >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
-  const size_t blob_len = nsets ? off[nsets] : 0;
-  void *d_sigs, *d_keys, *d_blob, *d_off, *d_koff;
-  if ((rc = c.get(WS_IN_A, (nsets + 1) * E::G1B, &d_sigs))) return rc;
-  if ((rc = c.get(WS_IN_B, (nkeys + 1) * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (nsets + 1) * 8, &d_off))) return rc;
-  if ((rc = c.get(WS_SEG_OFF, (nsets + 1) * 8, &d_koff))) return rc;
-  std::vector<uint64_t> rel(nsets + 1);
-  for (size_t i = 0; i <= nsets; ++i) rel[i] = nsets ? key_off[i] - k0 : 0;
-  if (nsets) HIPCHK(hipMemcpyAsync(d_sigs, sigs, nsets * E::G1B, hipMemcpyHostToDevice, st));
-  if (nkeys) HIPCHK(hipMemcpyAsync(d_keys, keys + k0 * E::G2B, nkeys * E::G2B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (nsets + 1) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_koff, rel.data(), (nsets + 1) * 8, hipMemcpyHostToDevice, st));
+  MsgView mv;
+  void *d_sigs, *d_keys, *d_koff;
+  std::vector<uint64_t> rel;
+  if ((rc = upload_msgs(c, st, blob, off, nsets, &mv))) return rc;
+  if ((rc = offsets_ok("key_off", key_off, nsets, OFF_TOTAL, SIZE_MAX, &max_set))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, nsets * E::G1B, &d_sigs, E::G1B))) return rc;
+  if ((rc = upload_key_sets(c, st, E::G2B, keys, key_off, nsets, &d_keys, &d_koff, rel))) return rc;
   HIPCHK(hipStreamSynchronize(st));                       // rel goes out of scope
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
   return verify_multi_batch_dev_t<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_koff, nsets, max_set, mv, allow_dups, false);
 }
 
@@ -242,87 +264,39 @@ int verify_multi_batch_t(const uint8_t* sigs, const uint8_t* keys, const uint64_
 template <class C>
 int aggregate_sets_t(int group, const uint8_t* pts, const uint64_t* set_off, size_t nsets, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   size_t max_set = 0;
-  for (size_t i = 0; i < nsets; ++i) {
-    if (set_off[i + 1] < set_off[i]) return fail(BGLS_ERR_ARG, "set_off not monotone");
-    if (set_off[i + 1] - set_off[i] > max_set) max_set = set_off[i + 1] - set_off[i];
-  }
+  if ((rc = offsets_ok("set_off", set_off, nsets, 0, SIZE_MAX, &max_set))) return rc;
   if (nsets == 0) return 0;
-  const size_t k0 = set_off[0], n = set_off[nsets] - k0;
-  if (n >= MAX_BATCH || nsets >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (set_off[nsets] - set_off[0] >= MAX_BATCH || nsets >= MAX_BATCH) return too_large();
   void *d_pts, *d_off, *d_out, *d_flags;
-  if ((rc = c.get(WS_IN_B, (n + 1) * PB, &d_pts))) return rc;
-  if ((rc = c.get(WS_SEG_OFF, (nsets + 1) * 8, &d_off))) return rc;
+  std::vector<uint64_t> rel;                              // alive until read_flags has synchronised
   if ((rc = c.get(WS_SEG_KEYS, (nsets + 1) * PB, &d_out))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
-  std::vector<uint64_t> rel(nsets + 1);
-  for (size_t i = 0; i <= nsets; ++i) rel[i] = set_off[i] - k0;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
-  if (n) HIPCHK(hipMemcpyAsync(d_pts, pts + k0 * PB, n * PB, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, rel.data(), (nsets + 1) * 8, hipMemcpyHostToDevice, st));
+  if ((rc = upload_key_sets(c, st, PB, pts, set_off, nsets, &d_pts, &d_off, rel))) return rc;
   if ((rc = E::sum_sets(c, st, group, (const uint8_t*)d_pts, (const uint64_t*)d_off, nsets, max_set, (uint8_t*)d_out, (uint32_t*)d_flags))) return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, nsets * PB, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  c.collect();
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, true, out, d_out, nsets * PB);
 }
 
-// The part of a batch of multi-signature sets that follows the key sums: sum_keys(d_apks, d_flags) leaves the n_sets key sums apk_b as wire
-// bytes at d_apks (encoding failures in d_flags); then Engine::miller_multi_sets and one final exponentiation per set in ONE launch.
-// verdicts[b] = 1 / 0, returns the number of accepted sets; apk_out / gt_out (nullable): the key sums / GT elements.  An encoding or hashing
-// failure anywhere fails the whole call with the single call's code.
+// A batch of n_sets multi-signature sets with one verdict per set: sum_keys(d_apks, d_flags) leaves the n_sets key sums apk_b as wire bytes
+// at d_apks (encoding failures in d_flags); then Engine::miller_multi_sets and batch_verdicts_run's tail.  apk_out / gt_out (nullable): the
+// key sums / GT elements.
 template <class C, class SumKeys>
 int verify_sets_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, size_t n_sets, MsgView mv, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out,
                     SumKeys&& sum_keys) {
-  typedef Engine<C> E;
-  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
-  // words: n_sets per-set flags (no duplicate rule: they stay zero), n_sets verdicts, the call's flag word
-  void *d_res, *d_part, *d_apks;
+  void* d_apks;
   int rc;
-  if ((rc = c.get(WS_BATCH_RES, (2 * n_sets + 1) * 4, &d_res))) return rc;
-  if ((rc = c.get(WS_PART, n_sets * E::GTB * (gt_out ? 2 : 1), &d_part))) return rc;
-  if ((rc = c.get(WS_SEG_KEYS, (n_sets + 1) * E::G2B, &d_apks))) return rc;
-  uint32_t* d_iflags = (uint32_t*)d_res;
-  uint32_t* d_verdicts = d_iflags + n_sets;
-  uint32_t* d_flags = d_verdicts + n_sets;
-  uint8_t* d_gt = gt_out ? (uint8_t*)d_part + n_sets * E::GTB : nullptr;
-  struct Drain {                                          // an error return below leaves launches in flight: drain the stream first
-    hipStream_t st;
-    bool armed = true;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(st);
-    }
-  } drain{st};
-  HIPCHK(hipMemsetAsync(d_res, 0, (2 * n_sets + 1) * 4, st));
-  if ((rc = sum_keys((uint8_t*)d_apks, d_flags))) return rc;
-  if ((rc = E::miller_multi_sets(c, st, d_sigs, (const uint8_t*)d_apks, mv, n_sets, (uint8_t*)d_part, d_flags))) return rc;
-  {
-    Scope sc(c, st, ST_FINAL);
-    kl::finalx_batch<C>(st, (const uint8_t*)d_part, n_sets, d_gt, d_verdicts, d_iflags, d_flags);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<uint32_t> words(n_sets + 1);
-  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n_sets + 1) * 4, hipMemcpyDeviceToHost, st));
-  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n_sets * E::GTB, hipMemcpyDeviceToHost, st));
-  if (apk_out) HIPCHK(hipMemcpyAsync(apk_out, d_apks, n_sets * E::G2B, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  drain.armed = false;
-  c.collect();
-  if ((rc = flags_to_rc(words[n_sets]))) return rc;
-  int accepted = 0;
-  for (size_t b = 0; b < n_sets; ++b) {
-    verdicts[b] = words[b] ? 1 : 0;
-    accepted += words[b] ? 1 : 0;
-  }
-  return accepted;
+  if ((rc = c.get(WS_SEG_KEYS, (n_sets + 1) * Engine<C>::G2B, &d_apks))) return rc;
+  return batch_verdicts_run<C>(c, st, n_sets, {verdicts, gt_out, apk_out, (const uint8_t*)d_apks}, [&](uint8_t* d_part, uint32_t*, uint32_t* d_flags) {
+    int r = sum_keys((uint8_t*)d_apks, d_flags);
+    return r ? r : Engine<C>::miller_multi_sets(c, st, d_sigs, (const uint8_t*)d_apks, mv, n_sets, d_part, d_flags);
+  });
 }
 
 // n_sets independent verifyMultiSignature calls (bgls/bgls.go:89-92) in one set of launches: every key sum in one pass
@@ -339,164 +313,105 @@ template <class C>
 int verify_multi_sets_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* blob, const uint64_t* off,
                         uint8_t* verdicts, uint8_t* gt_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   size_t max_set = 0;
-  for (size_t i = 0; i < n_sets; ++i)
-    if (key_off[i + 1] - key_off[i] > max_set) max_set = key_off[i + 1] - key_off[i];
-  const size_t k0 = key_off[0], nkeys = key_off[n_sets] - k0, blob_len = off[n_sets];
-  void *d_sigs, *d_keys, *d_blob, *d_off, *d_koff;
-  if ((rc = c.get(WS_IN_A, n_sets * E::G1B, &d_sigs))) return rc;
-  if ((rc = c.get(WS_IN_B, (nkeys + 1) * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n_sets + 1) * 8, &d_off))) return rc;
-  if ((rc = c.get(WS_SEG_OFF, (n_sets + 1) * 8, &d_koff))) return rc;
-  std::vector<uint64_t> rel(n_sets + 1);
-  for (size_t i = 0; i <= n_sets; ++i) rel[i] = key_off[i] - k0;
-  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_sets * E::G1B, hipMemcpyHostToDevice, st));
-  if (nkeys) HIPCHK(hipMemcpyAsync(d_keys, keys + k0 * E::G2B, nkeys * E::G2B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_koff, rel.data(), (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  MsgView mv;
+  void *d_sigs, *d_keys, *d_koff;
+  std::vector<uint64_t> rel;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, 0, SIZE_MAX, &max_set))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = upload_key_sets(c, st, E::G2B, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  if ((rc = upload_msgs(c, st, blob, off, n_sets, &mv))) return rc;
   HIPCHK(hipStreamSynchronize(st));                       // rel goes out of scope
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
   return verify_multi_sets_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets, max_set, mv, verdicts, gt_out);
+}
+
+// The n_sets + 1 key offsets of a device-pointer call are the caller's device words: copied back to koff and checked here (from 0,
+// monotone, no set above max_set, hae: every set below 2^28 keys, below 2^30 keys in all, keys non-NULL), so that no launch reads past the keys.
+int fetch_key_off(hipStream_t st, const void* d_key_off, size_t n_sets, size_t max_set, bool hae, const void* d_keys, std::vector<uint64_t>& koff) {
+  int rc;
+  koff.resize(n_sets + 1);
+  HIPCHK(hipMemcpyAsync(koff.data(), d_key_off, (n_sets + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if ((rc = offsets_ok("key_off", koff.data(), n_sets, OFF_FROM_ZERO | OFF_TOTAL | (hae ? OFF_HAE : 0), max_set))) return rc;
+  if (koff[n_sets] && !d_keys) return fail(BGLS_ERR_ARG, "NULL argument");
+  return 0;
 }
 
 template <class C>
 int verify_multi_sets_dev_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs, size_t msg_len,
                             size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  // the offsets are the caller's device words: check them here (monotone from 0, no set above max_set, below 2^30 keys), so that no
-  // launch reads past the keys
-  std::vector<uint64_t> koff(n_sets + 1);
-  HIPCHK(hipMemcpyAsync(koff.data(), d_key_off, (n_sets + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (koff[0] != 0) return fail(BGLS_ERR_ARG, "key_off must start at 0");
-  for (size_t b = 0; b < n_sets; ++b) {
-    if (koff[b + 1] < koff[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
-    if (koff[b + 1] - koff[b] > max_set) return fail(BGLS_ERR_ARG, "a set is larger than max_set");
-  }
-  if (koff[n_sets] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
-  if (koff[n_sets] && !d_keys) return fail(BGLS_ERR_ARG, "NULL argument");
+  std::vector<uint64_t> koff;
+  if ((rc = fetch_key_off(k.st, d_key_off, n_sets, max_set, false, d_keys, koff))) return rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return verify_multi_sets_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
+  return verify_multi_sets_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
 }
 
 // n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one set of launches: Engine::miller_bb (item n is the reference pair
-// (g1, g2)), one final exponentiation per item in ONE launch, then verdicts[b] = (e(sigma_b, Q_b) == e(g1, g2)) byte for byte on the
-// device; returns the number of accepted items.  gt_out (nullable): the n GT elements.  An encoding failure anywhere (sigma, U, V)
-// or a degenerate point step fails the whole call.
+// (g1, g2)), then batch_verdicts_run's tail in its Boneh-Boyen form: verdicts[b] = (e(sigma_b, Q_b) == e(g1, g2)) byte for byte on the
+// device.  gt_out (nullable): the n GT elements.  An encoding failure anywhere (sigma, U, V) or a degenerate point step fails the whole call.
 template <class C>
 int bb_verify_run(Ctx& c, hipStream_t st, const uint8_t* d_sigmas, const uint8_t* d_rs, const uint8_t* d_keys, const uint8_t* d_ms, size_t n,
                   uint8_t* verdicts, uint8_t* gt_out) {
-  typedef Engine<C> E;
-  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
-  const size_t m = n + 1;
-  // words: m per-item flags (always zero), m verdicts of the final exponentiation against one (unused), n verdicts, the call's flag word
-  void *d_res, *d_part;
-  int rc;
-  if ((rc = c.get(WS_BATCH_RES, (3 * m + 1) * 4, &d_res))) return rc;
-  if ((rc = c.get(WS_PART, 2 * m * E::GTB, &d_part))) return rc;
-  uint32_t* d_iflags = (uint32_t*)d_res;
-  uint32_t* d_fx = d_iflags + m;
-  uint32_t* d_verdicts = d_fx + m;
-  uint32_t* d_flags = d_verdicts + n;
-  uint8_t* d_gt = (uint8_t*)d_part + m * E::GTB;
-  struct Drain {                                          // an error return below leaves launches in flight: drain the stream first
-    hipStream_t st;
-    bool armed = true;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(st);
-    }
-  } drain{st};
-  HIPCHK(hipMemsetAsync(d_res, 0, (3 * m + 1) * 4, st));
-  if ((rc = E::miller_bb(c, st, d_sigmas, d_rs, d_keys, d_ms, n, (uint8_t*)d_part, d_flags))) return rc;
-  {
-    Scope sc(c, st, ST_FINAL);
-    kl::finalx_batch<C>(st, (const uint8_t*)d_part, m, d_gt, d_fx, d_iflags, d_flags);
-    kl::bb_verdicts<C>(st, d_gt, n, d_verdicts);
-  }
-  HIPCHK(hipGetLastError());
-  std::vector<uint32_t> words(n + 1);
-  HIPCHK(hipMemcpyAsync(words.data(), d_verdicts, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-  if (gt_out) HIPCHK(hipMemcpyAsync(gt_out, d_gt, n * E::GTB, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  drain.armed = false;
-  c.collect();
-  if ((rc = flags_to_rc(words[n]))) return rc;
-  int accepted = 0;
-  for (size_t b = 0; b < n; ++b) {
-    verdicts[b] = words[b] ? 1 : 0;
-    accepted += words[b] ? 1 : 0;
-  }
-  return accepted;
+  return batch_verdicts_run<C>(c, st, n, {verdicts, gt_out, nullptr, nullptr, true}, [&](uint8_t* d_part, uint32_t*, uint32_t* d_flags) {
+    return Engine<C>::miller_bb(c, st, d_sigmas, d_rs, d_keys, d_ms, n, d_part, d_flags);
+  });
 }
 
 template <class C>
 int bb_verify_t(const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, uint8_t* verdicts, uint8_t* gt_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_sigmas, *d_rs, *d_keys, *d_ms;
-  if ((rc = c.get(WS_IN_A, n * E::G1B, &d_sigmas))) return rc;
-  if ((rc = c.get(WS_IN_B, n * 32, &d_rs))) return rc;
-  if ((rc = c.get(WS_IN_C, n * 2 * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_D, n * 32, &d_ms))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sigmas, sigmas, n * E::G1B, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_rs, rs, n * 32, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_keys, keys, n * 2 * E::G2B, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_ms, ms, n * 32, hipMemcpyHostToDevice, st));
+  if ((rc = c.put(st, WS_IN_A, sigmas, n * E::G1B, &d_sigmas))) return rc;
+  if ((rc = c.put(st, WS_IN_B, rs, n * 32, &d_rs))) return rc;
+  if ((rc = c.put(st, WS_IN_C, keys, n * 2 * E::G2B, &d_keys))) return rc;
+  if ((rc = c.put(st, WS_IN_D, ms, n * 32, &d_ms))) return rc;
   return bb_verify_run<C>(c, st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
 }
 
 template <class C>
 int bb_verify_dev_t(const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  return bb_verify_run<C>(c, st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return bb_verify_run<C>(k.c, k.st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
 }
 
 template <class C>
 int verify_multi_t(const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_sig, *d_keys, *d_msg;
-  if ((rc = c.get(WS_IN_A, E::G1B, &d_sig))) return rc;
-  if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, msg_len, &d_msg))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sig, sig, E::G1B, hipMemcpyHostToDevice, st));
-  if (n) HIPCHK(hipMemcpyAsync(d_keys, keys, n * E::G2B, hipMemcpyHostToDevice, st));
-  if (msg_len) HIPCHK(hipMemcpyAsync(d_msg, msg, msg_len, hipMemcpyHostToDevice, st));
+  if ((rc = c.put(st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
+  if ((rc = c.put(st, WS_IN_C, msg, msg_len, &d_msg))) return rc;
   return verify_multi_dev_t<C>(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, n, (const uint8_t*)d_msg, msg_len);
 }
 
 template <class C>
 int pairing_product_t(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   void *d_g1b, *d_g2b, *d_g1s, *d_flags, *d_part;
   if ((rc = c.get(WS_IN_A, n * E::G1B, &d_g1b))) return rc;
   if ((rc = c.get(WS_IN_B, n * E::G2B, &d_g2b))) return rc;
@@ -520,43 +435,33 @@ int pairing_product_t(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t*
 template <class C>
 int hash_to_g1_t(const uint8_t* blob, const uint64_t* off, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  const size_t blob_len = off[n];
-  void *d_blob, *d_off, *d_g1s, *d_out, *d_flags;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
+  MsgView mv;
+  void *d_g1s, *d_out, *d_flags;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
   if ((rc = c.get(WS_G1S, n * sizeof(Aff<F1<C>>), &d_g1s))) return rc;
   if ((rc = c.get(WS_IN_A, n * E::G1B, &d_out))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
   if ((rc = E::hash_to_g1(c, st, mv, n, (Aff<F1<C>>*)d_g1s, (uint32_t*)d_flags))) return rc;
   kl::g1_to_bytes<C>(st, (const Aff<F1<C>>*)d_g1s, n, (uint8_t*)d_out);
   HIPCHK(hipGetLastError());
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, n * E::G1B, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, false, out, d_out, n * E::G1B);
 }
 
 template <class C>
 int aggregate_points_t(int group, const uint8_t* pts, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void *d_in, *d_out, *d_flags;
   if ((rc = c.get(WS_IN_B, n * PB, &d_in))) return rc;
@@ -564,23 +469,18 @@ int aggregate_points_t(int group, const uint8_t* pts, size_t n, uint8_t* out) {
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
   if (n) HIPCHK(hipMemcpyAsync(d_in, pts, n * PB, hipMemcpyHostToDevice, st));
-  rc = E::sum_points(c, st, group, (const uint8_t*)d_in, n, (uint8_t*)d_out, (uint32_t*)d_flags);
-  if (rc) return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, PB, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  if ((rc = E::sum_points(c, st, group, (const uint8_t*)d_in, n, (uint8_t*)d_out, (uint32_t*)d_flags))) return rc;
+  return read_flags(c, st, d_flags, false, out, d_out, PB);
 }
 
 template <class C>
 int scale_points_t(int group, const uint8_t* pts, const uint8_t* scalars, const uint8_t* signs, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void *d_in, *d_sc, *d_sg, *d_out, *d_flags;
@@ -597,21 +497,17 @@ int scale_points_t(int group, const uint8_t* pts, const uint8_t* scalars, const 
   if (group == BGLS_G1 && C::CURVE_ID == 1 && g1x()) kl::scale_g1x<C>(st, (const uint8_t*)d_in, (const uint8_t*)d_sc, sg, n, (uint8_t*)d_out, (uint32_t*)d_flags, 32);
   else kl::scale<C>(st, group, (const uint8_t*)d_in, (const uint8_t*)d_sc, sg, n, (uint8_t*)d_out, (uint32_t*)d_flags, 32);
   HIPCHK(hipGetLastError());
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, n * PB, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, false, out, d_out, n * PB);
 }
 
 template <class C>
 int point_check_t(int group, const uint8_t* a) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void *d_in, *d_flags;
   if ((rc = c.get(WS_IN_B, PB, &d_in))) return rc;
@@ -628,13 +524,13 @@ int point_check_t(int group, const uint8_t* a) {
 template <class C>
 int check_points_t(int group, const uint8_t* pts, size_t n, uint8_t* ok_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void *d_in, *d_ok, *d_flags;
   if ((rc = c.get(WS_IN_B, n * PB, &d_in))) return rc;
@@ -652,11 +548,11 @@ int check_points_t(int group, const uint8_t* pts, size_t n, uint8_t* ok_out) {
 template <class C>
 int generator_t(int group, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void* d_out;
   if ((rc = c.get(WS_OUT, PB, &d_out))) return rc;
@@ -669,11 +565,11 @@ int generator_t(int group, uint8_t* out) {
 template <class C>
 int gt_mul_t(const uint8_t* a, const uint8_t* b, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void* d_in;
   if ((rc = c.get(WS_IN_A, 2 * E::GTB, &d_in))) return rc;
   HIPCHK(hipMemcpyAsync(d_in, a, E::GTB, hipMemcpyHostToDevice, st));
@@ -685,11 +581,11 @@ int gt_mul_t(const uint8_t* a, const uint8_t* b, uint8_t* out) {
 template <class C>
 int gt_pow_t(const uint8_t* gt, const uint8_t* k_be32, int negate, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_in, *d_flags;
   if ((rc = c.get(WS_IN_A, 2 * E::GTB + 32, &d_in))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
@@ -699,46 +595,36 @@ int gt_pow_t(const uint8_t* gt, const uint8_t* k_be32, int negate, uint8_t* out)
   HIPCHK(hipMemcpyAsync(d + E::GTB, k_be32, 32, hipMemcpyHostToDevice, st));
   kl::gt_pow<C>(st, d, d + E::GTB, negate, d + E::GTB + 32, (uint32_t*)d_flags);
   HIPCHK(hipGetLastError());
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d + E::GTB + 32, E::GTB, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, false, out, d + E::GTB + 32, E::GTB);
 }
 
 template <class C>
 int miller_product_dev_t(const void* d_sig, const void* d_keys, const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n,
                          int check_dups, void* d_partial, void* d_flags, void* stream) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  Call k(stream);
+  if (k.rc) return k.rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return E::miller_product(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n, check_dups, (uint8_t*)d_partial,
+  return E::miller_product(k.c, k.st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n, check_dups, (uint8_t*)d_partial,
                            (uint32_t*)d_flags);
 }
 
 // containsDuplicateMessage (bgls/bgls.go:139-150) over device-resident fixed-stride messages: exact byte comparison
 int duplicate_scan_dev(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_flags, void* stream, uint32_t bucket = 0, uint32_t n_buckets = 1,
                        bool packed = false) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  Call k(stream);
+  if (k.rc) return k.rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return Engine<BN254>::dup_scan(c, st, mv, n, (uint32_t*)d_flags, bucket, n_buckets, packed);      // curve-independent
+  return Engine<BN254>::dup_scan(k.c, k.st, mv, n, (uint32_t*)d_flags, bucket, n_buckets, packed);      // curve-independent
 }
 
 // the sending half of the digest exchange: n 16-byte digests into n_buckets slots of `cap` records (k_digest_pack)
 int digest_pack_dev(const void* d_dig, size_t n, unsigned n_buckets, size_t cap, void* d_out, void* d_flags, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
   void* counts;
   if ((rc = c.get(WS_TABLE, 256 * 4, &counts))) return rc;          // the scan's table workspace: the scan of this verification comes after the exchange, in stream order
   HIPCHK(hipMemsetAsync(counts, 0, 256 * 4, st));
@@ -750,65 +636,49 @@ int digest_pack_dev(const void* d_dig, size_t n, unsigned n_buckets, size_t cap,
 template <class C>
 int final_verify_dev_t(const void* d_partials, size_t count, const void* d_flags, void* stream) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  return E::finalize(c, st, (const uint8_t*)d_partials, count, 1, (const uint32_t*)d_flags, nullptr);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return E::finalize(k.c, k.st, (const uint8_t*)d_partials, count, 1, (const uint32_t*)d_flags, nullptr);
 }
 
 template <class C>
 int final_verify_submit_dev_t(const void* d_partials, size_t count, const void* d_flags, void* stream) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  return E::finalize_submit(c, st, (const uint8_t*)d_partials, count, 1, (const uint32_t*)d_flags, nullptr);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return E::finalize_submit(k.c, k.st, (const uint8_t*)d_partials, count, 1, (const uint32_t*)d_flags, nullptr);
 }
 
 template <class C>
 int aggregate_points_dev_t(int group, const void* d_pts, size_t n, void* d_out, void* stream) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
   void* d_flags;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
-  rc = E::sum_points(c, st, group, (const uint8_t*)d_pts, n, (uint8_t*)d_out, (uint32_t*)d_flags);
-  if (rc) return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  if ((rc = E::sum_points(c, st, group, (const uint8_t*)d_pts, n, (uint8_t*)d_out, (uint32_t*)d_flags))) return rc;
+  return read_flags(c, st, d_flags, false);
 }
 
 template <class C>
 int verify_multi_dev_entry_t(const void* d_sig, const void* d_keys, size_t n, const void* d_msg, size_t msg_len, void* stream,
                              bool submit_only = false) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  return verify_multi_dev_t<C>(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, n, (const uint8_t*)d_msg, msg_len, submit_only);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return verify_multi_dev_t<C>(k.c, k.st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, n, (const uint8_t*)d_msg, msg_len, submit_only);
 }
 
 template <class C>
 int verify_multi_batch_sub_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t nsets, size_t max_set, const void* d_msgs,
                              size_t msg_len, size_t msg_stride, int allow_dups, void* stream, bool submit_only) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
-  int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
+  Call k(stream);
+  if (k.rc) return k.rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return verify_multi_batch_dev_t<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, nsets, max_set, mv, allow_dups,
+  return verify_multi_batch_dev_t<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, nsets, max_set, mv, allow_dups,
                                      submit_only);
 }
 
@@ -884,14 +754,13 @@ int hae_exponents_dev(Ctx& c, hipStream_t st, const uint8_t* h_keys, size_t n, v
 
 template <class C>
 int hae_exponents_t(const uint8_t* keys, size_t n, uint8_t* t_out) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
   int rc;
-  if ((rc = c.enter())) return rc;
   void* d_t;
-  if ((rc = hae_exponents_dev<C>(c, c.stream, keys, n, &d_t))) return rc;
-  if (n) HIPCHK(hipMemcpyAsync(t_out, d_t, n * 16, hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipStreamSynchronize(c.stream));
+  if ((rc = hae_exponents_dev<C>(k.c, k.st, keys, n, &d_t))) return rc;
+  if (n) HIPCHK(hipMemcpyAsync(t_out, d_t, n * 16, hipMemcpyDeviceToHost, k.st));
+  HIPCHK(hipStreamSynchronize(k.st));
   return 0;
 }
 
@@ -937,7 +806,7 @@ int weighted_sum_dev(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, co
     HIPCHK(hipMemsetAsync(d_out, 0, PTB, st));
     return 0;
   }
-  if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
+  if (n >= MAX_BATCH) return too_large();
   Scope sc(c, st, ST_SUM);
   const kl::MsmPlan p = kl::msm_plan(n);
   if (n < g_msm_min.load() || (uint64_t)n * (uint64_t)p.W >= (1ull << 32))            // list positions are 32-bit
@@ -981,11 +850,11 @@ int weighted_sum_dev(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, co
 template <class C>
 int verify_multi_weighted_t(const uint8_t* sig, const uint8_t* keys, const int64_t* mult, size_t n, const uint8_t* msg, size_t msg_len) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_sig, *d_keys, *d_msg, *d_apk, *d_fl2, *d_t = nullptr, *d_sg = nullptr;
   if ((rc = c.get(WS_IN_A, E::G1B, &d_sig))) return rc;
   if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
@@ -1017,60 +886,45 @@ int verify_multi_weighted_t(const uint8_t* sig, const uint8_t* keys, const int64
   if ((rc = weighted_sum_dev<C>(c, st, BGLS_G2, (const uint8_t*)d_keys, (const uint8_t*)d_t, (const uint8_t*)d_sg, n,
                                                    (uint8_t*)d_apk, (uint32_t*)d_fl2)))
     return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(&f, d_fl2, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if ((rc = flags_to_rc(f))) return rc;
+  if ((rc = read_flags(c, st, d_fl2, false))) return rc;
   return verify_multi_dev_t<C>(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_apk, 1, (const uint8_t*)d_msg, msg_len);
 }
 
 // getAggregatePubKey over device-resident points and weights (blsHAE.go:74-77): d_out <- sum_i w_i P_i as affine bytes
 template <class C>
 int weighted_sum_dev_t(int group, const void* d_pts, const void* d_w16, size_t n, void* d_out, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
   void* d_flags;
   if ((rc = c.get(WS_FLAGS2, 16, &d_flags))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
   if ((rc = weighted_sum_dev<C>(c, st, group, (const uint8_t*)d_pts, (const uint8_t*)d_w16, nullptr, n, (uint8_t*)d_out, (uint32_t*)d_flags)))
     return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  c.collect();
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, true);
 }
 
 // VerifyAggregateSignatureWithHAE (blsHAE.go:49-53): keys scaled by their exponents, then verifyAggSig with duplicates allowed
 template <class C>
 int verify_aggregate_hae_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  const size_t blob_len = n ? off[n] : 0;
-  void *d_sig, *d_keys, *d_blob, *d_off, *d_flags, *d_part, *d_t;
-  if ((rc = c.get(WS_IN_A, E::G1B, &d_sig))) return rc;
-  if ((rc = c.get(WS_IN_B, n * E::G2B, &d_keys))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
+  MsgView mv;
+  void *d_sig, *d_keys, *d_flags, *d_part, *d_t;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   if ((rc = c.get(WS_PART, E::GTB, &d_part))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sig, sig, E::G1B, hipMemcpyHostToDevice, st));
-  if (n) HIPCHK(hipMemcpyAsync(d_keys, keys, n * E::G2B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
   if ((rc = hae_exponents_dev<C>(c, st, keys, n, &d_t))) return rc;
   // e(H(m_i), t_i pk_i) = e(t_i H(m_i), pk_i): the exponent goes to the G1 side (a third of the G2 work, same GT value)
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
   if ((rc = E::miller_product(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n, 0, (uint8_t*)d_part, (uint32_t*)d_flags,
                               (const uint8_t*)d_t)))
     return rc;
@@ -1081,11 +935,11 @@ int verify_aggregate_hae_t(const uint8_t* sig, const uint8_t* keys, const uint8_
 template <class C>
 int aggregate_signatures_hae_t(const uint8_t* sigs, const uint8_t* keys, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_sigs, *d_out, *d_flags, *d_t;
   if ((rc = c.get(WS_IN_B, n * E::G1B, &d_sigs))) return rc;
   if ((rc = c.get(WS_OUT, E::G1B, &d_out))) return rc;
@@ -1096,11 +950,7 @@ int aggregate_signatures_hae_t(const uint8_t* sigs, const uint8_t* keys, size_t 
   if ((rc = weighted_sum_dev<C>(c, st, BGLS_G1, (const uint8_t*)d_sigs, (const uint8_t*)d_t, nullptr, n, (uint8_t*)d_out,
                                                    (uint32_t*)d_flags)))
     return rc;
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, E::G1B, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, false, out, d_out, E::G1B);
 }
 
 // ---- n_sets VerifyMultiSignatureWithHAE calls in one set of launches (bgls_verify_multi_hae_sets) -------------------------------
@@ -1111,7 +961,7 @@ std::atomic<size_t> g_hae_root_host_min{2048};
 
 // The exponents of n_sets key sets (hashPubKeysToExponents per set, blsHAE.go:80-93), staged on the host: the node table of the XOF
 // expansion and the roots of the sets above host_min when the keys' host bytes are given (h_keys), else none.  koff: the n_sets + 1
-// offsets from 0, checked.  launch() then runs k_hae_root_seg and k_hae_expand_seg: set b's exponents at d_t + 16 koff[b].
+// offsets from 0, checked.  stage() returns with the stream synchronised (its tables, and the caller's offsets, have landed).  launch() then runs k_hae_root_seg and k_hae_expand_seg: set b's exponents at d_t + 16 koff[b].
 template <class C>
 struct HaeSets {
   const uint8_t* d_keys;
@@ -1187,34 +1037,18 @@ int hae_sets_sum(Ctx& c, hipStream_t st, const HaeSets<C>& hs, size_t max_set, u
   return 0;
 }
 
-// the keys of a host-pointer call on the device: keys key_off[0] .. key_off[n_sets] to *d_keys, the offsets relative to key_off[0] to
-// *d_koff and to rel (the host copy)
-template <class C>
-int upload_key_sets(Ctx& c, hipStream_t st, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, void** d_keys, void** d_koff,
-                    std::vector<uint64_t>& rel) {
-  const size_t k0 = key_off[0], nkeys = key_off[n_sets] - k0;
-  int rc;
-  if ((rc = c.get(WS_IN_B, (nkeys + 1) * Engine<C>::G2B, d_keys))) return rc;
-  if ((rc = c.get(WS_SEG_OFF, (n_sets + 1) * 8, d_koff))) return rc;
-  rel.resize(n_sets + 1);
-  for (size_t i = 0; i <= n_sets; ++i) rel[i] = key_off[i] - k0;
-  if (nkeys) HIPCHK(hipMemcpyAsync(*d_keys, keys + k0 * Engine<C>::G2B, nkeys * Engine<C>::G2B, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(*d_koff, rel.data(), (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
-  return 0;
-}
-
 template <class C>
 int hae_exponents_sets_t(const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   void *d_keys, *d_koff;
   std::vector<uint64_t> rel;
-  if ((rc = upload_key_sets<C>(c, st, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  if ((rc = upload_key_sets(c, st, Engine<C>::G2B, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
   HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets};
-  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * Engine<C>::G2B, g_hae_root_host_min.load()))) return rc;
+  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * Engine<C>::G2B, g_hae_root_host_min.load()))) return rc;   // synchronises: rel has landed
   hs.launch(st);
   HIPCHK(hipGetLastError());
   if (rel[n_sets]) HIPCHK(hipMemcpyAsync(t_out + 16 * key_off[0], hs.d_t, rel[n_sets] * 16, hipMemcpyDeviceToHost, st));
@@ -1226,28 +1060,22 @@ template <class C>
 int verify_multi_hae_sets_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* blob, const uint64_t* off,
                             uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
-  hipStream_t st = c.stream;
+  if (c.res_pending) return in_flight();                  // before the staging below overwrites the exponents' workspaces
   size_t max_set = 0;
-  for (size_t i = 0; i < n_sets; ++i)
-    if (key_off[i + 1] - key_off[i] > max_set) max_set = key_off[i + 1] - key_off[i];
-  const size_t blob_len = off[n_sets];
-  void *d_sigs, *d_keys, *d_blob, *d_off, *d_koff;
+  MsgView mv;
+  void *d_sigs, *d_keys, *d_koff;
   std::vector<uint64_t> rel;
-  if ((rc = c.get(WS_IN_A, n_sets * E::G1B, &d_sigs))) return rc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n_sets + 1) * 8, &d_off))) return rc;
-  if ((rc = upload_key_sets<C>(c, st, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
-  HIPCHK(hipMemcpyAsync(d_sigs, sigs, n_sets * E::G1B, hipMemcpyHostToDevice, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n_sets + 1) * 8, hipMemcpyHostToDevice, st));
+  if ((rc = offsets_ok("key_off", key_off, n_sets, 0, SIZE_MAX, &max_set))) return rc;
+  if ((rc = upload_key_sets(c, st, E::G2B, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = upload_msgs(c, st, blob, off, n_sets, &mv))) return rc;
   HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets};
-  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * E::G2B, g_hae_root_host_min.load()))) return rc;   // also waits for rel's upload
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  if ((rc = hs.stage(c, st, rel.data(), keys + key_off[0] * E::G2B, g_hae_root_host_min.load()))) return rc;   // synchronises: rel has landed
   return verify_sets_run<C>(c, st, (const uint8_t*)d_sigs, n_sets, mv, verdicts, apk_out, gt_out,
                             [&](uint8_t* d_apks, uint32_t* d_flags) { return hae_sets_sum<C>(c, st, hs, max_set, d_apks, d_flags); });
 }
@@ -1255,25 +1083,14 @@ int verify_multi_hae_sets_t(const uint8_t* sigs, const uint8_t* keys, const uint
 template <class C>
 int verify_multi_hae_sets_dev_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs,
                                 size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream) {
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  if (c.res_pending) return fail(BGLS_ERR_ARG, "a verification is already in flight on this context (collect it first)");
-  hipStream_t st = stream ? (hipStream_t)stream : c.stream;
-  // the offsets are the caller's device words: checked here (as bgls_verify_multi_sets_dev, and every set below 2^28 keys) before any
-  // launch reads the keys; the node table of the expansion is built from this copy
-  std::vector<uint64_t> koff(n_sets + 1);
-  HIPCHK(hipMemcpyAsync(koff.data(), d_key_off, (n_sets + 1) * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (koff[0] != 0) return fail(BGLS_ERR_ARG, "key_off must start at 0");
-  for (size_t b = 0; b < n_sets; ++b) {
-    if (koff[b + 1] < koff[b]) return fail(BGLS_ERR_ARG, "key_off not monotone");
-    if (koff[b + 1] - koff[b] > max_set) return fail(BGLS_ERR_ARG, "a set is larger than max_set");
-    if (koff[b + 1] - koff[b] >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (blsHAE.go:81)");
-  }
-  if (koff[n_sets] >= MAX_BATCH) return fail(BGLS_ERR_ARG, "batch too large (n must be below 2^30)");
-  if (koff[n_sets] && !d_keys) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (c.res_pending) return in_flight();
+  std::vector<uint64_t> koff;                             // the node table of the expansion is built from this copy
+  if ((rc = fetch_key_off(st, d_key_off, n_sets, max_set, true, d_keys, koff))) return rc;
   HaeSets<C> hs{(const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets};
   if ((rc = hs.stage(c, st, koff.data(), nullptr, 0))) return rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
@@ -1287,11 +1104,11 @@ int verify_multi_hae_sets_dev_t(const void* d_sigs, const void* d_keys, const vo
 int wire_points(int curve, int group, bool compress, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok) {
   if (curve != BGLS_CURVE_ALTBN128 && curve != BGLS_CURVE_BLS12_381) return fail(BGLS_ERR_ARG, "unknown curve id");
   const bool bls = curve == BGLS_CURVE_BLS12_381;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
   const size_t CB = (bls ? 48 : 32) * (group == BGLS_G1 ? 1 : 2), UB = 2 * CB;
   const size_t in_b = compress ? UB : CB, out_b = compress ? CB : UB;
@@ -1313,13 +1130,9 @@ int wire_points(int curve, int group, bool compress, const uint8_t* in, size_t n
     }
   }
   HIPCHK(hipGetLastError());
-  uint32_t f = 0;
   HIPCHK(hipMemcpyAsync(out, d_out, n * out_b, hipMemcpyDeviceToHost, st));
   if (!compress) HIPCHK(hipMemcpyAsync(ok, d_ok, n, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  c.collect();
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, true);
 }
 
 // window multiples of a generator for this device (DeviceTables), built on first use
@@ -1354,11 +1167,11 @@ int fixed_base_table(Ctx& c, int group, const void** out) {
 template <class C>
 int scale_generator_t(int group, const uint8_t* sks, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
   const size_t PB = group == BGLS_G1 ? E::G1B : E::G2B;
   void *d_sc, *d_out;
@@ -1378,36 +1191,25 @@ int scale_generator_t(int group, const uint8_t* sks, size_t n, uint8_t* out) {
 template <class C>
 int sign_batch_t(const uint8_t* sks, const uint8_t* blob, const uint64_t* off, size_t n, uint8_t* out) {
   typedef Engine<C> E;
-  Ctx& c = ctx();
-  std::lock_guard<std::mutex> lk(c.mu);
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
   int rc;
-  if ((rc = c.enter())) return rc;
-  hipStream_t st = c.stream;
   if (n == 0) return 0;
-  for (size_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return fail(BGLS_ERR_ARG, "msg_off not monotone");
-  const size_t blob_len = off[n];
-  void *d_blob, *d_off, *d_g1s, *d_out, *d_flags, *d_sc;
-  if ((rc = c.get(WS_IN_C, blob_len, &d_blob))) return rc;
-  if ((rc = c.get(WS_IN_D, (n + 1) * 8, &d_off))) return rc;
+  MsgView mv;
+  void *d_g1s, *d_out, *d_flags, *d_sc;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
   if ((rc = c.get(WS_G1S, n * sizeof(Aff<F1<C>>), &d_g1s))) return rc;
   if ((rc = c.get(WS_IN_A, n * E::G1B, &d_out))) return rc;
-  if ((rc = c.get(WS_IN_B, n * 32, &d_sc))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
-  if (blob_len) HIPCHK(hipMemcpyAsync(d_blob, blob, blob_len, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_off, off, (n + 1) * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(d_sc, sks, n * 32, hipMemcpyHostToDevice, st));
-  MsgView mv = {(const uint8_t*)d_blob, (const uint64_t*)d_off, 0, 0};
+  if ((rc = c.put(st, WS_IN_B, sks, n * 32, &d_sc))) return rc;
   if ((rc = E::hash_to_g1(c, st, mv, n, (Aff<F1<C>>*)d_g1s, (uint32_t*)d_flags))) return rc;
   if (C::CURVE_ID == 1 && g1x()) kl::scale_aff_g1x<C>(st, (const Aff<F1<C>>*)d_g1s, (const uint8_t*)d_sc, n, (uint8_t*)d_out);
   else kl::scale_aff<C>(st, BGLS_G1, (const Aff<F1<C>>*)d_g1s, (const uint8_t*)d_sc, n, (uint8_t*)d_out);
   HIPCHK(hipGetLastError());
-  uint32_t f = 0;
-  HIPCHK(hipMemcpyAsync(out, d_out, n * E::G1B, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return flags_to_rc(f);
+  return read_flags(c, st, d_flags, false, out, d_out, n * E::G1B);
 }
 
 
