@@ -890,6 +890,34 @@ BGLS_HD bool sx_is_zero_mod_p(const Sx<C, LA>& a) {
   }
   return hit;
 }
+// the same for a value in (-11 p, 13 p): the differences of a mixed addition whose running point left a DOUBLING, whose coordinates are
+// not reductions' outputs (X3 = F - 2 D lies in (-4 p, 9 p), Y3 = E (D - X3) - 8 C in (-8 p, p): U2 - X3 reaches -9 p, S2 - Y3 reaches 9 p).
+// The sign and the size of the carried top limb tell which window of 8 p the value is in; only a value outside the usual window pays
+// for a second carry.
+template <class C, int LA>
+BGLS_HD bool sx_is_zero_mod_p_wide(const Sx<C, LA>& a) {
+  constexpr int N = C::RX_NL;
+  Sx<C, LA + 32> t;
+#pragma unroll
+  for (int i = 0; i < N; ++i) t.v[i] = a.v[i] + (i32)C::RX_PK[3 * N + i];   // + 3p (tight limbs)
+  Sx<C, SX_T> n = sx_norm<C>(t);
+  if (n.v[N - 1] < 0 || n.v[N - 1] > (i32)C::RX_PK[8 * N + N - 1]) {        // below 0 or above 8 p: move by 8 p
+    const bool up = n.v[N - 1] < 0;
+    Sx<C, LA + 48> u;
+#pragma unroll
+    for (int i = 0; i < N; ++i) u.v[i] = t.v[i] + (up ? (i32)C::RX_PK[8 * N + i] : -(i32)C::RX_PK[8 * N + i]);
+    n = sx_norm<C>(u);
+  }
+  bool hit = false;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    u32 d = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) d |= (u32)n.v[i] ^ C::RX_PK[k * N + i];
+    hit = hit || d == 0;
+  }
+  return hit;
+}
 // plain integer (canonical, < p, 32-bit limbs) -> R' form, tight: split into 28-bit limbs, one product by R'^2
 template <class C>
 BGLS_HD Sx<C, SX_T> sx_from_plain(const Fp<C>& y);

@@ -76,6 +76,9 @@ BGLS_HD X2<C, SX_T> x2_mulsub(const X2<C, LA>& a, const X2<C, LB>& b, const X2<C
 
 template <class C, int LA>
 BGLS_HD bool x2_is_zero(const X2<C, LA>& a) { return sx_is_zero_mod_p<C>(a.c0) && sx_is_zero_mod_p<C>(a.c1); }
+// for components in (-11 p, 13 p): differences against a doubling's X and Y (rx.hpp sx_is_zero_mod_p_wide)
+template <class C, int LA>
+BGLS_HD bool x2_is_zero_wide(const X2<C, LA>& a) { return sx_is_zero_mod_p_wide<C>(a.c0) && sx_is_zero_mod_p_wide<C>(a.c1); }
 
 // x R (the library's Montgomery form) -> R' form
 template <class C>
@@ -161,8 +164,8 @@ BGLS_HD JacX<C> jacx_madd(const JacX<C>& p, const AffX<C>& q) {
   const X2<C, SX_T> S2 = x2_mul<C>(x2_mul<C>(q.y, p.Z), Z1Z1);
   const auto Hd = x2_sub<C>(U2, p.X);
   const auto Rd = x2_sub<C>(S2, p.Y);
-  if (x2_is_zero<C>(Hd)) {                                     // same x: P = Q (double) or P = -Q (infinity)
-    if (x2_is_zero<C>(Rd)) return jacx_dbl<C>(p);
+  if (x2_is_zero_wide<C>(Hd)) {                                // same x: P = Q (double) or P = -Q (infinity); p may be a doubling's
+    if (x2_is_zero_wide<C>(Rd)) return jacx_dbl<C>(p);         // output: X up to 9 p, Y down to -8 p
     return jacx_inf<C>();
   }
   const X2<C, SX_F> H = x2_normf<C>(Hd);

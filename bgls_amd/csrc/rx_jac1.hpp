@@ -105,8 +105,8 @@ BGLS_HD Jac1<C> jac1_madd(const Jac1<C>& p, const Aff1<C>& q) {
   const Sx<C, SX_T> S2 = s1_mul<C>(s1_mul<C>(q.y, p.Z), Z1Z1);
   const auto Hd = sx_sub<C>(U2, p.X);
   const auto Rd = sx_sub<C>(S2, p.Y);
-  if (sx_is_zero_mod_p<C>(Hd)) {                               // same x: P = Q (double) or P = -Q (infinity)
-    if (sx_is_zero_mod_p<C>(Rd)) return jac1_dbl<C>(p);
+  if (sx_is_zero_mod_p_wide<C>(Hd)) {                          // same x: P = Q (double) or P = -Q (infinity); p may be a doubling's
+    if (sx_is_zero_mod_p_wide<C>(Rd)) return jac1_dbl<C>(p);   // output: X up to 9 p, Y down to -8 p
     return jac1_inf<C>();
   }
   const Sx<C, SX_F> H = sx_normf<C>(Hd);

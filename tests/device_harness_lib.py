@@ -1,0 +1,27 @@
+"""Loader of the test-only device harness (tests/harness/libdevice_harness.so) for the GPU-tier files: rebuilt (hipcc under a timeout) when
+any source is newer than it, loaded once per process, argument types declared."""
+import ctypes
+import importlib.util
+import os
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+
+
+def load():
+    global _LIB
+    if _LIB is None:
+        spec = importlib.util.spec_from_file_location("build_device_harness", os.path.join(ROOT, "tests", "harness", "build_device_harness.py"))
+        bdh = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(bdh)
+        lib = ctypes.CDLL(bdh.build(timeout=900))
+        vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
+        lib.dh_fp_op.argtypes = [i, i, sz, vp, vp, vp]
+        lib.dh_f2_op.argtypes = [i, i, sz, vp, vp, vp]
+        lib.dh_rx_sqrt.argtypes = [i, i, sz, vp, vp]
+        lib.dh_rx_raw.argtypes = [i, i, i, sz, vp, vp, vp]
+        lib.dh_bls_sw.argtypes = [sz, vp, i, vp, vp, vp]
+        lib.dh_padd.argtypes = [i, i, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.dh_pmul.argtypes = [i, i, sz, vp, vp, vp, vp, vp, vp]
+        _LIB = lib
+    return _LIB

@@ -1,5 +1,5 @@
 """Builds tests/harness/libhost_harness.so (TEST-ONLY: the device arithmetic headers compiled for the host).
-host_harness.cpp is compiled as four parts in parallel (-DHT_PART=0..3) and linked: under two minutes instead of five for the
+host_harness.cpp is compiled as five parts in parallel (-DHT_PART=0..4) and linked: under two minutes instead of five for the
 single translation unit.  Used by tests/conftest.py and __graft_entry__.build()."""
 import os, subprocess, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -9,12 +9,12 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
 SRC = os.path.join(HERE, "host_harness.cpp")
 SO = os.path.join(HERE, "libhost_harness.so")
-PARTS = 4
+PARTS = 5
 
 
 def deps():
     csrc = os.path.join(ROOT, "bgls_amd", "csrc")
-    return [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
+    return [SRC, os.path.join(HERE, "point_ops.hpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp")]
 
 
 def stale():

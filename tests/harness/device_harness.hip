@@ -9,6 +9,7 @@
 // error as a negative int (-1: bad argument).
 #include "../../bgls_amd/csrc/k_hash.hip"
 #include "../../bgls_amd/csrc/wire.hpp"
+#include "dev_bufs.hpp"
 
 namespace {
 
@@ -172,33 +173,7 @@ __global__ void __launch_bounds__(64) k_dh_aff_to_bytes(size_t n, const Aff<F1<B
   g1_to_bytes<C>(out + i * 2 * C::FP_BYTES, in[i]);
 }
 
-// ---- host side
-struct DevBufs {
-  void* p[8] = {};
-  int k = 0;
-  hipError_t err = hipSuccess;
-  void* get(size_t bytes) {
-    void* q = nullptr;
-    if (err == hipSuccess) err = hipMalloc(&q, bytes ? bytes : 1);
-    if (err == hipSuccess) p[k++] = q;
-    return q;
-  }
-  void up(void* dst, const void* src, size_t bytes) {
-    if (err == hipSuccess && bytes) err = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
-  }
-  void down(void* dst, const void* src, size_t bytes) {
-    if (err == hipSuccess && bytes) err = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-  }
-  void sync() {
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) err = hipDeviceSynchronize();
-  }
-  int done() {
-    for (int j = 0; j < k; ++j) (void)hipFree(p[j]);
-    return err == hipSuccess ? 0 : -(int)err;
-  }
-};
-
+// ---- host side (DevBufs: dev_bufs.hpp)
 template <class C>
 int fp_batch(int op, size_t n, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   if (op < 0 || op > 8) return -1;

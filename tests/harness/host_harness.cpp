@@ -13,8 +13,8 @@
 #include "../../bgls_amd/csrc/rx_pow.hpp"
 #include "../../bgls_amd/csrc/h2c_x.hpp"
 
-// The file compiles as ONE translation unit (no HT_PART: the sanitizer build includes it whole) or as four parts compiled in parallel and linked
-// together (-DHT_PART=0..3; tests/conftest.py, __graft_entry__.py): the single unit takes five minutes of an -O1 compile, the parts under two.
+// The file compiles as ONE translation unit (no HT_PART: the sanitizer build includes it whole) or as five parts compiled in parallel and linked
+// together (-DHT_PART=0..4; tests/conftest.py, __graft_entry__.py): the single unit takes five minutes of an -O1 compile, the parts under two.
 #ifdef HT_PART
 #define HT_HAS(p) (HT_PART == (p))
 #else
@@ -712,3 +712,54 @@ extern "C" int ht_rx_sumpair(int curve, const uint8_t* pts, int n, uint8_t* out)
 }
 
 #endif  // part 3
+
+#if HT_HAS(4)
+
+// ---- rx_jac1.hpp (G1) and rx_jac.hpp / rx_g2mul.hpp (the twists): every addition and doubling, and the windowed chain, one element per
+// call through tests/harness/point_ops.hpp (the device harness runs the same statements per lane).  group 1 / 2.  out: the result's wire
+// bytes; raw: PT_RAW words (infinity flag, then the Jacobian coordinates limb for limb); vmax: the largest |value| / p over the result's
+// coordinates in units of 2^-16 (rx.hpp promises less than 64 p in the point steps).  Returns 0, -2 on a non-canonical / off-curve point
+// or a bad lambda, -3 on a column overflow, -1 on a bad argument.
+#include "point_ops.hpp"
+template <class C>
+static int64_t pt_vmax(int group, const i32* raw) {
+  constexpr int N = C::RX_NL;
+  long double p = 0;
+  for (int i = N - 1; i >= 0; --i) p = p * (long double)(1u << C::RX_W) + (long double)C::RX_P[i];
+  long double worst = 0;
+  for (int c = 0; c < (group == 1 ? 3 : 6); ++c) {
+    long double v = 0;
+    for (int i = N - 1; i >= 0; --i) v = v * (long double)(1u << C::RX_W) + (long double)raw[1 + c * N + i];
+    if (v < 0) v = -v;
+    if (v > worst) worst = v;
+  }
+  return (int64_t)(worst / p * 65536.0L) + 1;
+}
+template <class C>
+static int rx_padd(int group, const uint8_t* a, const uint8_t* za, const uint8_t* b, const uint8_t* zb, int form, uint8_t* out, i32* raw, int64_t* vmax) {
+  if (form < 0 || form > 4 || (group != 1 && group != 2)) return -1;
+  g_rx_overflow = 0;
+  const bool ok = group == 1 ? pt1_add<C>(a, za, za != nullptr, b, zb, zb != nullptr, form, out, raw)
+                             : pt2_add<C>(a, za, za != nullptr, b, zb, zb != nullptr, form, out, raw);
+  *vmax = pt_vmax<C>(group, raw);
+  if (!ok) return -2;
+  return g_rx_overflow ? -3 : 0;
+}
+template <class C>
+static int rx_pmul(int group, const uint8_t* pt, const u32* k, int nbits, uint8_t* out, i32* raw, int64_t* vmax) {
+  if (nbits < 0 || nbits > 256 || (group != 1 && group != 2)) return -1;
+  g_rx_overflow = 0;
+  const bool ok = group == 1 ? pt1_mul<C>(pt, k, nbits, out, raw) : pt2_mul<C>(pt, k, nbits, out, raw);
+  *vmax = pt_vmax<C>(group, raw);
+  if (!ok) return -2;
+  return g_rx_overflow ? -3 : 0;
+}
+extern "C" int ht_rx_padd(int curve, int group, const uint8_t* a, const uint8_t* za, const uint8_t* b, const uint8_t* zb, int form, uint8_t* out, i32* raw,
+                          int64_t* vmax) {
+  return curve == 0 ? rx_padd<BN254>(group, a, za, b, zb, form, out, raw, vmax) : curve == 1 ? rx_padd<BLS381>(group, a, za, b, zb, form, out, raw, vmax) : -1;
+}
+// k: eight little-endian words, nbits: as the kernels pass it (the top set bit's position + 1) or SMALLER -- the chain then masks the scalar
+extern "C" int ht_rx_pmul(int curve, int group, const uint8_t* pt, const u32* k, int nbits, uint8_t* out, i32* raw, int64_t* vmax) {
+  return curve == 0 ? rx_pmul<BN254>(group, pt, k, nbits, out, raw, vmax) : curve == 1 ? rx_pmul<BLS381>(group, pt, k, nbits, out, raw, vmax) : -1;
+}
+#endif  // part 4

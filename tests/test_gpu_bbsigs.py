@@ -326,3 +326,108 @@ def test_python_mirror_signature_consistency(gpu_lib, curve):
     other = Bls12 if curve["id"] == 0 else Altbn128
     osk, opk = bbsigs.KeyGen(other)
     assert bbsigs.VerifyBatch(cv, sb + [bbsigs.Sign(other, osk, 4)], [pk] * 3 + [opk], [1, 2, 3, 4]) == [True, True, True, False]
+
+
+def _ref_q(cid, key, r, m):
+    """Q = m g2 + U + r V by the plain affine reference (tests/ec_ref.py), scalars unreduced"""
+    from ec_ref import Curve
+    cv = Curve(cid, 2)
+    G2B = cv.size
+    return cv.to_bytes(cv.add(cv.add(cv.mul(cv.gen, m), cv.from_bytes(key[:G2B])), cv.mul(cv.from_bytes(key[G2B:]), r)))
+
+
+def test_every_fixture_point_as_v_at_its_order(gpu_lib, curve):
+    """k_bb_keys' windowed chain (rx_g2mul.hpp) on EVERY on-twist fixture point outside the subgroup as V -- the small-order ones included,
+    also the one whose own Miller loop degenerates: Q = m g2 + U + r V is not that point (asserted with the plain reference) -- under a
+    random r, r = order(V), order(V) +- 1 and 2^256 - 1.  Q's bytes against the plain reference, GT bytes and verdicts against the
+    stepwise path."""
+    import point_cases as pc
+    from ec_ref import Curve
+    lib, cid, fp = gpu_lib, curve["id"], curve["fp"]
+    cv = Curve(cid, 2)
+    G2B = 4 * fp
+    rnd = random.Random(71 + cid)
+    pts = pc.fixture_points(cid, 2)
+    assert any(o is not None and o < 64 for _, o, _ in pts) or cid == 0
+    plan = []
+    for pt, order, note in pts:
+        rs = [rnd.getrandbits(256), (1 << 256) - 1]
+        if order is not None:
+            rs += [order, order - 1, order + 1]
+        plan += [(pt, r) for r in rs]
+    it = make_items(lib, cid, fp, len(plan), 73 + cid)
+    for b, (pt, r) in enumerate(plan):
+        it["key"][b] = it["key"][b][:G2B] + cv.to_bytes(pt)
+        it["r"][b] = r
+    rc, verdicts, gts = run(lib, cid, fp, it)
+    assert rc >= 0, rc
+    for b, (pt, r) in enumerate(plan):
+        want_q = _ref_q(cid, it["key"][b], r, it["m"][b])
+        assert want_q != cv.to_bytes(pt) and want_q != bytes(G2B), b
+        assert stepwise_q(lib, cid, fp, it["key"][b], r, it["m"][b]) == want_q, (b, hex(r))
+    check_items(lib, cid, fp, it, verdicts, gts, oracle_every=0)
+    assert verdicts == [0] * len(plan)
+
+
+def test_fixed_base_chain_meets_its_own_table_entry(gpu_lib, curve):
+    """k_bb_keys folds m g2 in with one mixed addition (jacx_madd) per non-zero byte of m against the table d 2^(8 j) g2.  With V at
+    infinity or r = 0 the running point is U when byte j arrives: U = d 2^(8 j) g2 makes that addition a DOUBLING, U = -d 2^(8 j) g2
+    makes the sum pass through infinity and go on with the higher bytes of m.  Q's bytes against the plain reference, GT bytes and
+    verdicts against the stepwise path."""
+    from ec_ref import Curve
+    lib, cid, fp = gpu_lib, curve["id"], curve["fp"]
+    cv = Curve(cid, 2)
+    G2B = 4 * fp
+    rnd = random.Random(79 + cid)
+    spots = [(0, 1), (0, 255), (1, 7), (5, 128), (15, 200), (31, 1), (31, 255)]          # (byte position j of m, its value d)
+    plan = []
+    for j, d in spots:
+        for neg in (False, True):
+            for v_inf in (False, True):
+                for higher in (False, True):
+                    if higher and j == 31:
+                        continue
+                    m = d << (8 * j)                                       # only byte j below: the running point is still U there
+                    if higher:
+                        m |= rnd.getrandbits(8 * (31 - j)) << (8 * (j + 1)) | 1 << 255
+                    plan.append((j, d, neg, v_inf, m))
+    it = make_items(lib, cid, fp, len(plan), 83 + cid)
+    for b, (j, d, neg, v_inf, m) in enumerate(plan):
+        u = cv.mul(cv.gen, d << (8 * j))
+        it["key"][b] = cv.to_bytes(cv.neg(u) if neg else u) + (bytes(G2B) if v_inf else it["key"][b][G2B:])
+        it["r"][b] = it["r"][b] if v_inf else 0
+        it["m"][b] = m
+    rc, verdicts, gts = run(lib, cid, fp, it)
+    assert rc >= 0, rc
+    for b, (j, d, neg, v_inf, m) in enumerate(plan):
+        want_q = _ref_q(cid, it["key"][b], it["r"][b], m)
+        if neg and m == d << (8 * j):
+            assert want_q == bytes(G2B)
+        assert stepwise_q(lib, cid, fp, it["key"][b], it["r"][b], m) == want_q, plan[b]
+    check_items(lib, cid, fp, it, verdicts, gts, oracle_every=0)
+
+
+def test_u_equals_r_v_when_the_chain_ends_on_a_doubling(gpu_lib, curve):
+    """r = 16 c ends the windowed chain on four doublings (a zero last digit), so r V reaches the mixed addition of U straight from
+    jacx_dbl, whose Y is not reduced; with U = r V that addition must DOUBLE.  Q = 2 U (m = 0) and Q = 2 U + m g2 against the plain
+    reference; GT bytes and verdicts against the stepwise path."""
+    from ec_ref import Curve
+    lib, cid, fp = gpu_lib, curve["id"], curve["fp"]
+    cv = Curve(cid, 2)
+    G2B = 4 * fp
+    rnd = random.Random(89 + cid)
+    n = 48
+    it = make_items(lib, cid, fp, n, 97 + cid)
+    for b in range(n):
+        v = cv.from_bytes(it["key"][b][G2B:])
+        r = 16 * rnd.choice([1, 2, 3, 16, 255, rnd.getrandbits(60), rnd.getrandbits(250)])
+        u = cv.mul(v, r)
+        it["key"][b] = cv.to_bytes(u if b % 4 else cv.neg(u)) + it["key"][b][G2B:]
+        it["r"][b] = r
+        it["m"][b] = 0 if b % 3 else rnd.getrandbits(256)
+    rc, verdicts, gts = run(lib, cid, fp, it)
+    assert rc >= 0, rc
+    for b in range(n):
+        want_q = _ref_q(cid, it["key"][b], it["r"][b], it["m"][b])
+        assert stepwise_q(lib, cid, fp, it["key"][b], it["r"][b], it["m"][b]) == want_q, b
+    check_items(lib, cid, fp, it, verdicts, gts, oracle_every=0)

@@ -13,12 +13,12 @@ test_rx_arith.py) runs the same headers as waves of one; what only the device bu
 
 References are plain Python integers: pow, pow(a, -1, p), Euler's criterion, Fp2 = Fp[u] / (u^2 + 1)."""
 import ctypes
-import importlib.util
 import os
 import random
 
 import pytest
 
+import device_harness_lib
 from oracle import coracle
 
 pytestmark = pytest.mark.gpu
@@ -42,17 +42,7 @@ LIMBS = {0: 8, 1: 12}                        # 32-bit words
 def dh(gpu_lib):
     """libdevice_harness.so, rebuilt (hipcc under a timeout) when any source is newer than it.  Loaded after the library (gpu_lib imports
     torch first): the process keeps one HIP runtime."""
-    spec = importlib.util.spec_from_file_location("build_device_harness", os.path.join(ROOT, "tests", "harness", "build_device_harness.py"))
-    bdh = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bdh)
-    lib = ctypes.CDLL(bdh.build(timeout=900))
-    vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
-    lib.dh_fp_op.argtypes = [i, i, sz, vp, vp, vp]
-    lib.dh_f2_op.argtypes = [i, i, sz, vp, vp, vp]
-    lib.dh_rx_sqrt.argtypes = [i, i, sz, vp, vp]
-    lib.dh_rx_raw.argtypes = [i, i, i, sz, vp, vp, vp]
-    lib.dh_bls_sw.argtypes = [sz, vp, i, vp, vp, vp]
-    return lib
+    return device_harness_lib.load()
 
 
 def buf(b):

@@ -726,3 +726,72 @@ def test_digest_pack_and_packed_scan(gpu_lib):
     w = torch.zeros(1, dtype=torch.int32, device=dev)
     assert gpu_lib.bgls_digest_pack_dev(t.data_ptr(), n, 1, 10, t.data_ptr(), w.data_ptr(), None) < 0          # one bucket: nothing to exchange
     assert gpu_lib.bgls_duplicate_scan_packed_dev(t.data_ptr(), n, 2, 2, w.data_ptr(), None) < 0
+
+
+def test_scale_points_at_exceptional_points_and_scalars(gpu_lib, curve):
+    """bgls_scale_points on G1 (k_scale_g1x on BLS12-381: rx_jac1.hpp's windowed chain) where the chain leaves its general addition: the
+    order-3 point (0, 2) of BLS12-381 and its negative (table entries at infinity), the fixture's on-curve points outside the subgroup,
+    and on the generator the scalars of the host tier's list -- k = j q (the last addition cancels), k = j (q - 2) (it doubles), every
+    window-crossing bit length -- under sign bytes 0 and 1.  Expected bytes: the plain affine reference (tests/ec_ref.py), scalars unreduced."""
+    import point_cases as pc
+    from ec_ref import Curve
+    cid, fp = curve["id"], curve["fp"]
+    cv = Curve(cid, 1)
+    rnd = random.Random(61 + cid)
+    items = []                                                             # (point, k)
+    for c in pc.mul_cases(cid, 1):
+        if c["tag"].startswith("g, "):
+            items.append((cv.from_bytes(c["pt"]), c["k"] & ((1 << c["nbits"]) - 1)))
+    others = [pt for pt, _, _ in pc.fixture_points(cid, 1) + pc.special_points(cid, 1)]
+    if cid == 1:
+        assert (0, 2) in others or cv.neg((0, 2)) in others
+        others += [pt for pt in ((0, 2), cv.neg((0, 2))) if pt not in others]
+    for pt in others:
+        for k in [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, (1 << 256) - 1, ORDER_OF[cid], ORDER_OF[cid] - 2] + [rnd.getrandbits(256) for _ in range(12)] + [rnd.getrandbits(128) for _ in range(4)]:
+            items.append((pt, k))
+    memo = {}
+    for sign in (0, 1):
+        n = len(items)
+        o = out(n * 2 * fp)
+        rc = gpu_lib.bgls_scale_points(cid, 1, B(b"".join(cv.to_bytes(pt) for pt, _ in items)), B(b"".join(k.to_bytes(32, "big") for _, k in items)),
+                                       B(bytes([sign]) * n), n, o)
+        assert rc == 0, rc
+        raw = bytes(o)
+        for i, (pt, k) in enumerate(items):
+            if (pt, k) not in memo:
+                memo[(pt, k)] = cv.mul(pt, k)
+            want = cv.neg(memo[(pt, k)]) if sign else memo[(pt, k)]
+            assert raw[i * 2 * fp:(i + 1) * 2 * fp] == cv.to_bytes(want), (sign, i, hex(k))
+            if pt is not None and pt[0] == 0:                              # (0, +-2): order 3, the closed form
+                base = cv.neg(pt) if sign else pt
+                assert want == [None, base, cv.neg(base)][k % 3]
+
+
+ORDER_OF = {0: 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+            1: 52435875175126190479447740508185965837690552500527637822603658699938581184513}
+
+
+def test_sign_batch_with_secret_keys_at_the_group_order(gpu_lib, curve):
+    """bgls_sign_batch (k_scale_aff_g1x) with the secret keys q, 2 q and q - 2 among ordinary ones: sk H(m) for the integer sk as given --
+    infinity, infinity and -2 H(m)"""
+    from ec_ref import Curve
+    cid, fp = curve["id"], curve["fp"]
+    cv = Curve(cid, 1)
+    q = ORDER_OF[cid]
+    rnd = random.Random(67 + cid)
+    n = 70
+    sks = [rnd.randrange(1, q) for _ in range(n)]
+    for at, k in ((0, q), (31, 2 * q), (32, q - 2), (63, q), (64, q - 2), (69, 2 * q), (5, q + 1), (6, q - 1)):
+        sks[at] = k
+    msgs = [rnd.randbytes(1 + i % 40) for i in range(n)]
+    hs = hash_batch(gpu_lib, cid, fp, msgs)
+    sg = out(n * 2 * fp)
+    assert gpu_lib.bgls_sign_batch(cid, B(b"".join(k.to_bytes(32, "big") for k in sks)), B(b"".join(msgs)), offsets(msgs), n, sg) == 0
+    raw = bytes(sg)
+    for i in range(n):
+        h = cv.from_bytes(hs[i])
+        assert cv.on_curve(h)
+        assert raw[i * 2 * fp:(i + 1) * 2 * fp] == cv.to_bytes(cv.mul(h, sks[i])), (i, hex(sks[i]))
+    assert raw[:2 * fp] == bytes(2 * fp) and raw[31 * 2 * fp:32 * 2 * fp] == bytes(2 * fp)
+    h32 = cv.from_bytes(hs[32])
+    assert raw[32 * 2 * fp:33 * 2 * fp] == cv.to_bytes(cv.neg(cv.dbl(h32)))
