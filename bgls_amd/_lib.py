@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libbgls_hip%s.so" % ("_" + _VARIANT if _VARIANT 
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
 u64p = ctypes.POINTER(ctypes.c_uint64)
+u32p = ctypes.POINTER(ctypes.c_uint32)
 vp = ctypes.c_void_p
 sz = ctypes.c_size_t
 ci = ctypes.c_int
@@ -50,6 +51,9 @@ SIGNATURES = {
     "bgls_verify_aggregate_hae": (ci, [ci, u8p, u8p, u8p, u64p, sz]),
     "bgls_verify_multi_hae_sets": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p, u8p]),
     "bgls_verify_multi_hae_sets_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, u8p, vp]),
+    "bgls_ams_verify_batch": (ci, [ci, u8p, u8p, u8p, u32p, u64p, sz, u8p, u64p, u8p, u8p]),
+    "bgls_set_ams_sum_cut": (ci, [sz]),
+    "bgls_ams_verify_batch_dev": (ci, [ci, vp, vp, vp, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, vp]),
     "bgls_hae_exponents_sets": (ci, [ci, u8p, u64p, sz, u8p]),
     "bgls_set_hae_root_host_min": (ci, [sz]),
     "bgls_verify_multi_multiplicity": (ci, [ci, u8p, u8p, ctypes.POINTER(ctypes.c_int64), sz, u8p, sz]),

@@ -472,6 +472,39 @@ def AmsVerifySignature(curve, apk, signers, aggKey, aggSig, msg):   # blsAsmSigs
     return ok and pt.Equals(curve.GetGTIdentity())
 
 
+def AmsVerifySignatures(curve, apks, signers, aggKeys, aggSigs, msgs):
+    """len(apks) independent AmsVerifySignature calls (blsAsmSigs.go:48-59) in one bgls_ams_verify_batch call: a list of bools, one per
+    item.  An item that is not made of Points of this curve (a nil or foreign signature or key) or has a signer index outside
+    [0, 2^32) gets what AmsVerifySignature says about it alone; an empty signer list gives False (the reference panics); a call that
+    fails as a whole is settled item by item."""
+    n = len(apks)
+    if not (n == len(signers) == len(aggKeys) == len(aggSigs) == len(msgs)):
+        raise ValueError("apks, signers, aggKeys, aggSigs and msgs differ in length")
+    out = [False] * n
+    batch = []
+    for b in range(n):
+        if not (isinstance(aggSigs[b], Point) and aggSigs[b].curve is curve and aggSigs[b].group == G1
+                and _g2_keys_ok(curve, [apks[b], aggKeys[b]])
+                and all(isinstance(i, int) and 0 <= i < 1 << 32 for i in signers[b])):
+            out[b] = AmsVerifySignature(curve, apks[b], signers[b], aggKeys[b], aggSigs[b], bytes(msgs[b]))
+        elif len(signers[b]):
+            batch.append(b)
+    if not batch:
+        return out
+    flat = [i for b in batch for i in signers[b]]
+    soff = (ctypes.c_uint64 * (len(batch) + 1))()
+    for i, b in enumerate(batch):
+        soff[i + 1] = soff[i] + len(signers[b])
+    ms = [bytes(msgs[b]) for b in batch]
+    verdicts = (ctypes.c_uint8 * len(batch))()
+    rc = _lib.load().bgls_ams_verify_batch(curve.id, _lib.buf(b"".join(apks[b].raw for b in batch)), _lib.buf(b"".join(aggKeys[b].raw for b in batch)),
+                                           _lib.buf(b"".join(aggSigs[b].raw for b in batch)), (ctypes.c_uint32 * len(flat))(*flat), soff, len(batch),
+                                           _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None)
+    for i, b in enumerate(batch):
+        out[b] = verdicts[i] == 1 if rc >= 0 else AmsVerifySignature(curve, apks[b], signers[b], aggKeys[b], aggSigs[b], ms[i])
+    return out
+
+
 def AmsVerifySignatureWithSetCheck(curve, check, apk, signers, aggKey, aggSig, msg):   # blsAsmSigs.go:61-66
     if not check(signers):
         return False

@@ -123,6 +123,36 @@ int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_
                                                   stream));
 } BGLS_ABI_GUARD
 
+int bgls_ams_verify_batch(int curve, const uint8_t* apks, const uint8_t* agg_keys, const uint8_t* agg_sigs, const uint32_t* signers,
+                          const uint64_t* signer_off, size_t n, const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!signer_off || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("signer_off", signer_off, n, 0))) return rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (n + (signer_off[n] - signer_off[0]) >= MAX_BATCH) return too_large();
+  if (!apks || !agg_keys || !agg_sigs || !verdicts || (msg_off[n] > msg_off[0] && !msg_blob) || (signer_off[n] > signer_off[0] && !signers))
+    return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, ams_verify_t<CV>(apks, agg_keys, agg_sigs, signers, signer_off, n, msg_blob, msg_off, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_ams_verify_batch_dev(int curve, const void* d_apks, const void* d_agg_keys, const void* d_agg_sigs, const void* d_signers, const void* d_signer_off,
+                              size_t n, size_t max_signers, const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out,
+                              void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!d_apks || !d_agg_keys || !d_agg_sigs || !d_signer_off || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, ams_verify_dev_t<CV>(d_apks, d_agg_keys, d_agg_sigs, d_signers, d_signer_off, n, max_signers, d_msgs, msg_len, msg_stride, verdicts, gt_out,
+                                       stream));
+} BGLS_ABI_GUARD
+
+int bgls_set_ams_sum_cut(size_t n) try {
+  if (n == 0) return fail(BGLS_ERR_ARG, "the cut must be at least one item");
+  g_ams_sum_cut.store(n);
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_hae_exponents_sets(int curve, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, uint8_t* t_out) try {
   if (n_sets >= MAX_BATCH) return too_large();
   if (!key_off) return fail(BGLS_ERR_ARG, "NULL argument");

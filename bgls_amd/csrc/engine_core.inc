@@ -101,7 +101,8 @@ int offsets_ok(const char* name, const uint64_t* off, size_t count, unsigned rul
 
 // workspace slots
 enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
-       WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_HAE_NODES, WS_NUM };
+       WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_HAE_NODES, WS_AMS_SIGNERS, WS_AMS_OFF, WS_AMS_BLOB, WS_AMS_PTS,
+       WS_AMS_SUMS, WS_AMS_AGG, WS_NUM };
 
 struct Ctx {
   std::mutex mu;
@@ -256,6 +257,8 @@ bool side_fork_allowed() {
 // Miller shape (bgls_set_miller_shape / BGLS_MILLER_SHAPE): 0 = automatic -- k_miller_latx up to 128 pairings, k_miller_x60 (carry-free
 // limbs, both curves) above; 4 = k_miller_x60 for every batch size (the second argument is then its role / priority / block-form
 // mode word); 5 = the 32-bit fused kernel k_miller_ab64 for every batch size (the legacy-path matrix of the tests).
+// items per Engine::sum_sets pass of the batched accountable-subgroup check (bgls_set_ams_sum_cut; tests lower it to reach a second pass)
+std::atomic<size_t> g_ams_sum_cut{(size_t)1 << 16};
 std::atomic<int> g_shape{-1}, g_x60_rot{-1};      // x60 mode -1: automatic (see Engine::miller)
 int miller_shape() {
   // the environment preset is read exactly once (thread-safe static initialiser), before any setter's value can be overwritten
@@ -316,9 +319,10 @@ constexpr int miller_dbg() { return 0; }
 // ST_SCATTER and ST_EPI are opened by the batch of independent verifications only (Engine::miller_product_batch): the padded layout
 // of its pairs and its batched epilogue; ST_BB_KEYS by the batched Boneh-Boyen verification only (Engine::miller_bb: its Q_b = m_b g2 + U_b + r_b V_b)
 // ST_HAE_KEYS by the batched HAE multi-signatures only (bgls_verify_multi_hae_sets: the roots, the XOF expansion and the weighted main pass)
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_NUM };
+// ST_AMS_MSGS by the batched accountable-subgroup multisignatures only (Engine::miller_ams: the assembly of the hash inputs)
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_NUM };
 const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys",
-                                         "hae_keys"};
+                                         "hae_keys", "ams_msgs"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -343,7 +347,7 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -658,6 +662,81 @@ struct Engine {
     if (bls) {
       Scope sc(c, st, ST_EPI);
       kl::epiloguex_seg<C>(st, n_sets, (const Fp2<C>*)rest, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
+
+  // A batch of n accountable-subgroup multisignature checks (bgls_ams_verify_batch, bgls/blsAsmSigs.go:48-59): item b is the group key
+  // d_apks[b], the signers' key sum d_agg_keys[b] (G2 wire bytes), the signature d_sigs[b] (G1 wire bytes), the indices
+  // d_signers[d_soff[b] .. d_soff[b + 1]) (d_soff: n + 1 device offsets from 0, total = d_soff[n], max_signers = the longest list) and
+  // message b of mv.  d_hoff: the n + total + 1 offsets of the hash inputs (hbytes in all), a prefix of their exact lengths made by the
+  // caller.  Every stage runs once for the batch: k_ams_msgs (the hash inputs; an empty list sets d_iflags[b]), ONE hashing pass over the
+  // n + total inputs, the hash points of the signers as wire bytes through Engine::sum_sets (aggMsg_b; exact for a repeated index), the
+  // parse of the sums and of the -sigma_b, one k_miller_ams launch sequence (one accumulator per item over both walked pairs and, on
+  // alt-bn128, the signature pair), on BLS12-381 the batched epilogue: every hash point there is uncleared, so the product of the two
+  // walked pairs is raised to the cofactor (a sum of uncleared points is cleared by the same power), then the signature pair.  Writes n
+  // GT partials (bytes, no final exponentiation) to d_partials.
+  static int miller_ams(Ctx& c, hipStream_t st, const uint8_t* d_apks, const uint8_t* d_agg_keys, const uint8_t* d_sigs, const uint32_t* d_signers,
+                        const uint64_t* d_soff, size_t n, size_t total, size_t max_signers, MsgView mv, const uint64_t* d_hoff, size_t hbytes,
+                        uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags) {
+    const size_t nh = n + total;
+    if (n >= MAX_BATCH || nh >= MAX_BATCH) return too_large();
+    constexpr bool bls = C::CURVE_ID == 1;
+    void *blob, *g1s, *pts, *sums, *agg, *sigs, *rest = nullptr, *epi = nullptr;
+    int rc;
+    if ((rc = c.get(WS_AMS_BLOB, hbytes + 16, &blob))) return rc;
+    if ((rc = c.get(WS_G1S, (nh + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+    if ((rc = c.get(WS_AMS_PTS, (total + 1) * G1B, &pts))) return rc;
+    if ((rc = c.get(WS_AMS_SUMS, (n + 1) * G1B, &sums))) return rc;
+    if ((rc = c.get(WS_AMS_AGG, (n + 1) * sizeof(Aff<G1F>), &agg))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
+    if (bls) {
+      if ((rc = c.get(WS_F_A, (n + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
+      if ((rc = c.get(WS_BATCH_EPI, (n + 1) * 12 * sizeof(Fp2<C>), &epi))) return rc;
+    }
+    const LineCoeffs<C>* gl = nullptr;
+    if ((rc = gen_lines(c, &gl))) return rc;
+    {
+      Scope sc(c, st, ST_AMS_MSGS);
+      kl::ams_msgs(st, d_apks, d_signers, d_soff, n, total, mv, (unsigned)G2B, d_hoff, (uint8_t*)blob, d_iflags);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      Scope sc(c, st, ST_H2C);
+      const MsgView hv = {(const uint8_t*)blob, d_hoff, 0, 0};
+      if ((rc = hash_to_g1(c, st, hv, nh, (Aff<G1F>*)g1s, d_flags, bls))) return rc;
+      // the segmented sum takes wire bytes: the signers' hash points leave the stage in that form
+      if (total) kl::g1_to_bytes<C>(st, (const Aff<G1F>*)g1s + n, total, (uint8_t*)pts);
+    }
+    // aggMsg_b = sum of the item's H2 points.  Engine::sum_sets keeps 64 Jacobian partials per set on G1, so the items go through it
+    // 2^16 at a time (0.6 GB of partials on BLS12-381; bgls_set_ams_sum_cut): the offsets index the one array of points, whichever items
+    // a pass covers.  Each pass is a key sum of its own in the stage timers (sum_points).
+    const size_t SUM_CUT = g_ams_sum_cut.load();
+    for (size_t b0 = 0; b0 < n; b0 += SUM_CUT) {
+      const size_t cnt = n - b0 < SUM_CUT ? n - b0 : SUM_CUT;
+      if ((rc = sum_sets(c, st, BGLS_G1, (const uint8_t*)pts, d_soff + b0, cnt, max_signers, (uint8_t*)sums + b0 * G1B, d_flags))) return rc;
+    }
+    {
+      constexpr size_t XB = 32768;                          // blocks per launch (as in Engine::miller)
+      const size_t ipb = kl::miller_ams_per_block<C>(), nb = (n + ipb - 1) / ipb;
+      void* park;
+      if ((rc = c.get(WS_QP, kl::miller_ams_park_bytes<C>(nb < XB ? nb : XB), &park))) return rc;
+      Scope sc(c, st, ST_MILLER);
+      kl::g1_parse<C>(st, (const uint8_t*)sums, n, 0, (Aff<G1F>*)agg, d_flags);
+      kl::g1_parse<C>(st, d_sigs, n, 1, (Aff<G1F>*)sigs, d_flags);                           // -sigma_b
+      for (size_t blk0 = 0; blk0 < nb; blk0 += XB) {
+        const size_t nblocks = nb - blk0 < XB ? nb - blk0 : XB;
+        const size_t s0 = blk0 * ipb;
+        kl::miller_ams<C>(st, (unsigned)nblocks, (const Aff<G1F>*)g1s + s0, d_agg_keys + s0 * G2B, (const Aff<G1F>*)agg + s0, d_apks + s0 * G2B,
+                          (const Aff<G1F>*)sigs + s0, gl, n - s0, bls ? (Fp2<C>*)rest + s0 * 6 : nullptr, bls ? nullptr : d_partials + s0 * GTB, d_flags,
+                          (uint32_t*)park);
+      }
+      HIPCHK(hipGetLastError());
+    }
+    if (bls) {
+      Scope sc(c, st, ST_EPI);
+      kl::epiloguex_seg<C>(st, n, (const Fp2<C>*)rest, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
       HIPCHK(hipGetLastError());
     }
     return 0;

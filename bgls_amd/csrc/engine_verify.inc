@@ -1098,6 +1098,112 @@ int verify_multi_hae_sets_dev_t(const void* d_sigs, const void* d_keys, const vo
                             [&](uint8_t* d_apks, uint32_t* d_flags) { return hae_sets_sum<C>(c, st, hs, max_set, d_apks, d_flags); });
 }
 
+// ---- n AmsVerifySignature calls in one set of launches (bgls_ams_verify_batch, bgls/blsAsmSigs.go:48-59) ------------------------
+// The offsets of the n + total hash inputs of a batch, appended to tab: input b < n is 0x00 || m_b (msg_off, or msg_len where it is
+// NULL), input n + s is 0x01 || apk || strconv.Itoa(signers[s]) -- g2b key bytes and 1 to 10 digits.
+void ams_hash_offsets(std::vector<uint64_t>& tab, const uint32_t* signers, size_t n, size_t total, const uint64_t* msg_off, size_t msg_len, size_t g2b) {
+  uint64_t at = 0;
+  tab.reserve(tab.size() + n + total + 1);
+  for (size_t b = 0; b < n; ++b) {
+    tab.push_back(at);
+    at += 1 + (msg_off ? msg_off[b + 1] - msg_off[b] : msg_len);
+  }
+  for (size_t s = 0; s < total; ++s) {
+    tab.push_back(at);
+    unsigned digits = 1;
+    for (uint32_t v = signers[s]; v >= 10; v /= 10) ++digits;
+    at += 1 + g2b + digits;
+  }
+  tab.push_back(at);
+}
+
+// Engine::miller_ams and batch_verdicts_run's tail.  d_tab: the n + 1 signer offsets from 0, then the n + total + 1 offsets of the hash
+// inputs (ams_hash_offsets; hbytes in all), on the device.
+template <class C>
+int ams_verify_run(Ctx& c, hipStream_t st, const uint8_t* d_apks, const uint8_t* d_agg_keys, const uint8_t* d_sigs, const uint32_t* d_signers,
+                   const uint64_t* d_soff, const uint64_t* d_hoff, size_t n, size_t total, size_t max_signers, size_t hbytes, MsgView mv, uint8_t* verdicts,
+                   uint8_t* gt_out) {
+  return batch_verdicts_run<C>(c, st, n, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t* d_iflags, uint32_t* d_flags) {
+    return Engine<C>::miller_ams(c, st, d_apks, d_agg_keys, d_sigs, d_signers, d_soff, n, total, max_signers, mv, d_hoff, hbytes, d_part, d_iflags, d_flags);
+  });
+}
+
+template <class C>
+int ams_verify_t(const uint8_t* apks, const uint8_t* agg_keys, const uint8_t* agg_sigs, const uint32_t* signers, const uint64_t* signer_off, size_t n,
+                 const uint8_t* blob, const uint64_t* off, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  if (c.res_pending) return in_flight();
+  size_t max_signers = 0;
+  if ((rc = offsets_ok("signer_off", signer_off, n, 0, SIZE_MAX, &max_signers))) return rc;
+  const size_t s0 = signer_off[0], total = signer_off[n] - s0;
+  std::vector<uint64_t> tab(n + 1);                       // alive until the stream has been synchronised below
+  for (size_t b = 0; b <= n; ++b) tab[b] = signer_off[b] - s0;
+  ams_hash_offsets(tab, total ? signers + s0 : nullptr, n, total, off, 0, E::G2B);
+  MsgView mv;
+  void *d_apks, *d_agg, *d_sigs, *d_signers, *d_tab;
+  if ((rc = c.put(st, WS_IN_A, agg_sigs, n * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.put(st, WS_IN_B, apks, n * E::G2B, &d_apks))) return rc;
+  if ((rc = c.put(st, WS_SEG_KEYS, agg_keys, n * E::G2B, &d_agg))) return rc;
+  if ((rc = c.put(st, WS_AMS_SIGNERS, total ? signers + s0 : nullptr, total * 4, &d_signers))) return rc;
+  if ((rc = c.put(st, WS_AMS_OFF, tab.data(), tab.size() * 8, &d_tab))) return rc;
+  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  HIPCHK(hipStreamSynchronize(st));                       // tab has landed
+  return ams_verify_run<C>(c, st, (const uint8_t*)d_apks, (const uint8_t*)d_agg, (const uint8_t*)d_sigs, (const uint32_t*)d_signers, (const uint64_t*)d_tab,
+                           (const uint64_t*)d_tab + n + 1, n, total, max_signers, tab.back(), mv, verdicts, gt_out);
+}
+
+// The n + 1 signer offsets of the device form, checked: from 0, monotone, no list above max_signers, n + total below 2^30, indices non-NULL.
+int ams_offsets_ok(const std::vector<uint64_t>& soff, size_t n, size_t max_signers, const void* d_signers) {
+  int rc;
+  if ((rc = offsets_ok("signer_off", soff.data(), n, OFF_FROM_ZERO, max_signers))) return rc;
+  if (n + soff[n] >= MAX_BATCH) return too_large();
+  if (soff[n] && !d_signers) return fail(BGLS_ERR_ARG, "NULL argument");
+  return 0;
+}
+
+// The signer offsets are the caller's device words, copied back and checked before any launch (as fetch_key_off).  A process without a
+// device has no device memory: there the words are read where they lie, so that a bad argument is still BGLS_ERR_ARG, and everything
+// else BGLS_ERR_NO_DEVICE.
+template <class C>
+int ams_verify_dev_t(const void* d_apks, const void* d_agg_keys, const void* d_sigs, const void* d_signers, const void* d_signer_off, size_t n,
+                     size_t max_signers, const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+  typedef Engine<C> E;
+  Call k(stream);
+  std::vector<uint64_t> soff(n + 1);
+  int rc;
+  if (k.rc == BGLS_ERR_NO_DEVICE) {
+    const std::string why = g_err;
+    memcpy(soff.data(), d_signer_off, (n + 1) * 8);
+    if ((rc = ams_offsets_ok(soff, n, max_signers, d_signers))) return rc;
+    return fail(BGLS_ERR_NO_DEVICE, why.c_str());
+  }
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  if (c.res_pending) return in_flight();
+  HIPCHK(hipMemcpyAsync(soff.data(), d_signer_off, (n + 1) * 8, hipMemcpyDefault, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if ((rc = ams_offsets_ok(soff, n, max_signers, d_signers))) return rc;
+  const size_t total = soff[n];
+  // the digits of an index set the length of its hash input: the indices come back once for the offsets of the inputs
+  std::vector<uint32_t> idx(total);
+  if (total) HIPCHK(hipMemcpyAsync(idx.data(), d_signers, total * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<uint64_t> tab;
+  ams_hash_offsets(tab, idx.data(), n, total, nullptr, msg_len, E::G2B);
+  void* d_tab;
+  if ((rc = c.put(st, WS_AMS_OFF, tab.data(), tab.size() * 8, &d_tab))) return rc;
+  HIPCHK(hipStreamSynchronize(st));                       // tab has landed
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return ams_verify_run<C>(c, st, (const uint8_t*)d_apks, (const uint8_t*)d_agg_keys, (const uint8_t*)d_sigs, (const uint32_t*)d_signers,
+                           (const uint64_t*)d_signer_off, (const uint64_t*)d_tab, n, total, max_signers, tab.back(), mv, verdicts, gt_out);
+}
+
 // Marshal / Unmarshal* compressed branch over a batch.  alt-bn128: the reference's own 32 / 64-byte forms
 // (curves/altbn128.go:81-89,203-221,296-376).  BLS12-381: 48 / 96 bytes in the ebfull/pairing layout the reference names as
 // its target (curves/bls12_381.go:54-62,115-123,242-264; wire.hpp) -- unpinned against the un-vendored dis2/bls12.

@@ -116,6 +116,23 @@ void hae_expand_seg(hipStream_t st, const uint64_t* roots, const uint32_t* nodes
 template <class C>
 void hae_wsum_main(hipStream_t st, const uint8_t* keys, const uint64_t* key_off, const uint8_t* t, size_t n_sets, unsigned P, void* out, uint32_t* flags);
 
+// ---- k_ams.hip: the hash inputs of a batch of accountable-subgroup multisignature checks (bgls_ams_verify_batch).  Input b < n is
+// 0x00 || message b of mv, input n + s is 0x01 || apks[item of s] (g2b wire bytes) || decimal(signers[s]); signer_off: n + 1 device offsets
+// from 0 (total = signer_off[n]), hoff: the n + total + 1 offsets of the inputs in blob (a prefix of their exact lengths).  An item without
+// signers gets inst_flags[b] set.
+void ams_msgs(hipStream_t st, const uint8_t* apks, const uint32_t* signers, const uint64_t* signer_off, size_t n, size_t total, MsgView mv, unsigned g2b,
+              const uint64_t* hoff, uint8_t* blob, uint32_t* inst_flags);
+
+// ---- k_millerams.hip: the Miller loop of n accountable-subgroup multisignature checks, one accumulator per item, ams_per_block items per
+// block.  Item b: (g1a[b], q2a[b]) and (g1b[b], q2b[b]) walked (keys as wire bytes) and, on alt-bn128, (sigs[b], g2) on the generator lines
+// -- GT bytes (no final exponentiation) to out_bytes + b GTB; on BLS12-381 the two walked pairs alone, six w-basis Fp2 to out_w + 6 b (the
+// epilogue's rest).  park: miller_ams_park_bytes.
+template <class C>
+void miller_ams(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1a, const uint8_t* q2a, const Aff<F1<C>>* g1b, const uint8_t* q2b, const Aff<F1<C>>* sigs,
+                const LineCoeffs<C>* gen_lines, size_t n, Fp2<C>* out_w, uint8_t* out_bytes, uint32_t* flags, uint32_t* park);
+template <class C> size_t miller_ams_park_bytes(size_t nblocks);
+template <class C> size_t miller_ams_per_block();
+
 // prepared key sets (prepared.hpp): bytes per key of the line table, per pairing of the point table, per key of k_prepare's scratch
 struct PrepSizes { size_t line_bytes_per_key, point_bytes, tmp_bytes_per_key; };
 template <class C> PrepSizes prep_sizes();

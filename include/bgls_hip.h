@@ -202,6 +202,22 @@ int bgls_hae_exponents_sets(int curve, const uint8_t* keys, const uint64_t* key_
 /* Sets with more than n keys have their BLAKE2Xb root computed on the host by the host-pointer entries (bgls_verify_multi_hae_sets,
  * bgls_hae_exponents_sets); the others on the device, one lane per set.  Results do not depend on it.  Returns 0. */
 int bgls_set_hae_root_host_min(size_t n);
+/* n independent AmsVerifySignature calls (accountable-subgroup multisignatures, bgls/blsAsmSigs.go:48-59,73-86) in one set of launches.
+ * Item b is the group key apks[b] and the signers' key sum agg_keys[b] (G2 wire bytes), the signature agg_sigs[b] (G1 wire bytes), the
+ * signer indices signers[signer_off[b] .. signer_off[b+1]) and the message msg_blob[msg_off[b] .. msg_off[b+1]).  verdicts[b] = 1 iff
+ *   e(H(0x00 || m_b), aggKey_b) * e(sum_k H(0x01 || apk_b wire bytes || strconv.Itoa(signers[k])), apk_b) * e(-sigma_b, g2) = 1;
+ * a repeated index is added twice, as the reference does.  An item with an empty signer list gets verdict 0 (the reference panics); its
+ * gt_out entry is unspecified.  gt_out: NULL or n GT elements, the product above after the final exponentiation.
+ * A non-canonical or off-curve apk, aggKey or sigma, a degenerate point step or an exhausted hash ANYWHERE fails the whole call with the
+ * single path's code and leaves verdicts undefined; non-monotone offsets, NULL arguments where a count is non-zero, n or n + the number
+ * of signers at 2^30 or more are BGLS_ERR_ARG, checked before any device work; n == 0 returns 0 without touching a pointer.
+ * There is no CPU fallback: BGLS_ERR_NO_DEVICE without a device.  Returns the number of accepted items (>= 0) or < 0. */
+int bgls_ams_verify_batch(int curve, const uint8_t* apks, const uint8_t* agg_keys, const uint8_t* agg_sigs, const uint32_t* signers,
+                          const uint64_t* signer_off, size_t n, const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts,
+                          uint8_t* gt_out);
+/* Items per pass of the segmented G1 sum inside bgls_ams_verify_batch (default 2^16: the sum keeps 64 partial sums per item).  Results do
+ * not depend on it; tests lower it to reach a second pass.  n == 0 is BGLS_ERR_ARG.  Returns 0. */
+int bgls_set_ams_sum_cut(size_t n);
 /* getAggregatePubKey over device-resident inputs (bgls/blsHAE.go:74-77 = AggregatePoints(ScalePoints(points, w)),
  * curves/curve.go:73-121,190-214): d_out (affine bytes of the group) = sum_i w_i P_i, weights = n 16-byte big-endian
  * magnitudes.  Computed by the bucket method (k_msm.hip: a counting sort of the (point, window) pairs by digit, one
@@ -381,6 +397,13 @@ int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys
 int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
                                    size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
                                    uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream);
+/* bgls_ams_verify_batch with everything on the device: d_signers (uint32 indices) and d_signer_off (n + 1 uint64 offsets from 0) are read
+ * back and checked before any launch (monotone, no list above max_signers: BGLS_ERR_ARG; a process without a device has no device
+ * memory, so there d_signer_off is read where it lies and a bad argument is still BGLS_ERR_ARG); message b is msg_len bytes at
+ * d_msgs + b msg_stride.  Same semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns. */
+int bgls_ams_verify_batch_dev(int curve, const void* d_apks, const void* d_agg_keys, const void* d_agg_sigs, const void* d_signers,
+                              const void* d_signer_off, size_t n, size_t max_signers, const void* d_msgs, size_t msg_len,
+                              size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* bgls_bb_verify_batch with its inputs on the device (same layouts).  Same semantics and return value; synchronises `stream`
  * (NULL: the context's stream) before it returns. */
 int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms,
