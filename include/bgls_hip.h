@@ -285,7 +285,11 @@ int bgls_pair(int curve, const uint8_t* g1, const uint8_t* g2, uint8_t* gt_out);
 /* PointT.Add = Fp12 multiplication (curves/altbn128.go:264-271, curves/bls12_381.go:160-168) */
 int bgls_gt_mul(int curve, const uint8_t* a, const uint8_t* b, uint8_t* out);
 /* PointT.Mul (curves/altbn128.go:273-281, curves/bls12_381.go:170-173): gt^k, k a 32-byte big-endian magnitude,
- * negative != 0 for k < 0 (the inverse of a GT element is its conjugate: GT elements are unitary). */
+ * negative != 0 for k < 0 (the inverse of a GT element is its conjugate: GT elements are unitary).  The reference only ever raises
+ * pairing values (its PointT comes out of Pair and Add alone) and hands the signed scalar to its upstream library, so it sets no
+ * contract for other input.  Here: any canonical Fp12 element is accepted; negative == 0 returns the plain power, negative != 0 the
+ * CONJUGATE of the power, which is the inverse power on unitary elements (all of GT) and nowhere else
+ * (tests/test_gpu_f12_arith.py pins both). */
 int bgls_gt_pow(int curve, const uint8_t* gt, const uint8_t* k_be32, int negative, uint8_t* out);
 /* GetGTIdentity (curves/altbn128.go:441-443,478; curves/bls12_381.go:295-297,341) */
 int bgls_gt_identity(int curve, uint8_t* out);

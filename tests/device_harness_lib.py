@@ -23,5 +23,10 @@ def load():
         lib.dh_bls_sw.argtypes = [sz, vp, i, vp, vp, vp]
         lib.dh_padd.argtypes = [i, i, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.dh_pmul.argtypes = [i, i, sz, vp, vp, vp, vp, vp, vp]
+        lib.dh_f12.argtypes = [i, i, i, i, sz, vp, vp, vp, i, i, vp, vp]
+        lib.dh_f12_results.argtypes = [i, i, i]
+        lib.dh_f12_slot_words.argtypes = [i, i]
+        lib.dh_f12_half_stride.argtypes = [i]
+        lib.dh_finalx.argtypes = [i, i, sz, i, vp, vp, vp, vp, vp]
         _LIB = lib
     return _LIB

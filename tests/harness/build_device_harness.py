@@ -1,6 +1,6 @@
 """Builds tests/harness/libdevice_harness.so (TEST-ONLY: device_harness.hip, the device arithmetic and k_hash.hip's kernels behind batched
-C exports for the GPU tier, and device_harness_points.hip, the point layer) with the product Makefile's flags: the two translation
-units are compiled in parallel and linked.  Used by tests/device_harness_lib.py and __graft_entry__.build()."""
+C exports for the GPU tier, device_harness_points.hip, the point layer, and device_harness_f12.hip, the cooperative Fp12 forms) with the
+product Makefile's flags: the three translation units are compiled in parallel and linked.  Used by tests/device_harness_lib.py and __graft_entry__.build()."""
 import os
 import subprocess
 import tempfile
@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "bgls_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SRCS = [os.path.join(HERE, "device_harness.hip"), os.path.join(HERE, "device_harness_points.hip")]
+SRCS = [os.path.join(HERE, f) for f in ("device_harness.hip", "device_harness_points.hip", "device_harness_f12.hip")]
 SO = os.path.join(HERE, "libdevice_harness.so")
 
 

@@ -60,6 +60,8 @@ def test_fp_and_fp2(host_harness, curve):
 
 
 def test_fp12_tower(host_harness, curve):
+    """three random pairs and one unitary element: a smoke check of ht_f12_op; the coverage of tower.hpp's Fp12 at edge operands (0, 1,
+    p - 1 at every position, subfield, unitary and GT elements, ops 0 - 8 over all of them) is tests/test_f12_cases.py"""
     lib, cid, n = host_harness, curve["id"], curve["fp"]
     c = CURVES[curve["name"]]
     PR = Pairing(c)
