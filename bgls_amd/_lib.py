@@ -35,6 +35,9 @@ SIGNATURES = {
     "bgls_verify_multi_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci]),
     "bgls_verify_multi_sets": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p]),
     "bgls_verify_multi_sets_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, vp]),
+    "bgls_verify_multi_sets_combined": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u64p, sz, u8p, u8p, u8p]),
+    "bgls_verify_multi_sets_combined_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, u64p, sz, u8p, u8p, u8p, vp]),
+    "bgls_rlc_coefficients": (ci, [u8p, sz, u8p]),
     "bgls_bb_verify_batch": (ci, [ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]),
     "bgls_bb_verify_batch_dev": (ci, [ci, vp, vp, vp, vp, sz, u8p, u8p, vp]),
     "bgls_aggregate_sets": (ci, [ci, ci, u8p, u64p, sz, u8p]),

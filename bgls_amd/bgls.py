@@ -1,6 +1,7 @@
 """Host-side mirror of the reference's `bgls` scheme functions on the hot path
 (bgls/bgls.go, bgls/blsKosk.go), same names and semantics, each routed to ONE batch C call."""
 import ctypes
+import os
 import secrets
 from . import _lib
 from .curves import _reduce_scalar, AggregatePoints, ScalePoints, Point, G1, G2
@@ -207,6 +208,67 @@ def KoskVerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
     """len(aggsigs) independent KoskVerifyMultiSignature calls (bgls/blsKosk.go:117-120) in one batch: 0x01 prepended to every message,
     a list of bools, one per set (pubkeys[b]: the signers of msgs[b])."""
     return _verify_multi_sets(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
+
+
+def _group_offsets(n, group):
+    """n_groups + 1 offsets of consecutive chunks of `group` sets (None: one group)"""
+    if group is None:
+        return [0, n]
+    if int(group) < 1:
+        raise ValueError("group must be a positive chunk size or None")
+    return list(range(0, n, int(group))) + [n]
+
+
+def VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group=None, seed=None):
+    """"Are these multi-signatures all valid?" under one combined check per group of consecutive sets (bgls_verify_multi_sets_combined:
+    one final exponentiation per group instead of one per set).  group: an int chunk size, or None for one group over all sets;
+    seed: 32 bytes from a CSPRNG drawn AFTER the inputs are fixed (None draws os.urandom(32)).  Returns the list of group verdicts; a
+    group that holds a set bgls_verify_multi rejects is rejected except with probability about 2^-127.  Every set must be made of
+    Points of this curve; an encoding or hashing error anywhere raises ValueError (use VerifyMultiSignatures to settle such a batch)."""
+    n = len(aggsigs)
+    if not (n == len(pubkeys) == len(msgs)):
+        raise ValueError("aggsigs, pubkeys and msgs differ in length")
+    if seed is None:
+        seed = os.urandom(32)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    if n == 0:
+        return []
+    for sig, keys in zip(aggsigs, pubkeys):
+        if not (isinstance(sig, Point) and sig.curve is curve and sig.group == G1
+                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
+            raise ValueError("the combined check takes G1 / G2 Points of this curve only")
+    goff = _group_offsets(n, group)
+    key_off = (ctypes.c_uint64 * (n + 1))()
+    for b in range(n):
+        key_off[b + 1] = key_off[b] + len(pubkeys[b])
+    ms = [bytes(m) for m in msgs]
+    verdicts = (ctypes.c_uint8 * (len(goff) - 1))()
+    rc = _lib.load().bgls_verify_multi_sets_combined(curve.id, _lib.buf(b"".join(s.raw for s in aggsigs)),
+                                                     _lib.buf(b"".join(k.raw for keys in pubkeys for k in keys)), key_off, n, _lib.buf(b"".join(ms)),
+                                                     _offsets(ms), (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1, _lib.buf(bytes(seed)), verdicts, None)
+    if rc < 0:
+        raise ValueError("bgls_verify_multi_sets_combined: %s" % _lib.last_error())
+    return [v == 1 for v in verdicts]
+
+
+def KoskVerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group=None, seed=None):
+    """VerifyMultiSignaturesCombined with 0x01 prepended to every message (bgls/blsKosk.go:117-120)."""
+    return VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs], group, seed)
+
+
+def VerifyMultiSignaturesLocated(curve, aggsigs, pubkeys, msgs, group=64, seed=None):
+    """One verdict per set at the combined check's cost where everything is valid: ONE combined call over groups of `group` sets, then
+    ONE VerifyMultiSignatures call over only the sets of the rejected groups; the sets of accepted groups get True."""
+    n = len(aggsigs)
+    goff = _group_offsets(n, group)
+    groups = VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group, seed)
+    out = [True] * n
+    again = [b for g, ok in enumerate(groups) if not ok for b in range(goff[g], goff[g + 1])]
+    if again:
+        for b, v in zip(again, VerifyMultiSignatures(curve, [aggsigs[b] for b in again], [pubkeys[b] for b in again], [msgs[b] for b in again])):
+            out[b] = v
+    return out
 
 
 def VerifySingleSignatures(curve, sigs, pubkeys, msgs):

@@ -101,6 +101,38 @@ int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys
   DISPATCH(curve, verify_multi_sets_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+int bgls_verify_multi_sets_combined(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
+                                    const uint64_t* msg_off, const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts,
+                                    uint8_t* gt_out) try {
+  if (n_sets >= MAX_BATCH) return too_large();
+  if (!key_off || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, OFF_TOTAL))) return rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n_sets, 0))) return rc;
+  if ((rc = rlc_args_ok(group_off, n_groups, n_sets, seed))) return rc;
+  if (n_sets == 0) return 0;
+  if (!sigs || !verdicts || (msg_off[n_sets] && !msg_blob) || (key_off[n_sets] > key_off[0] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_multi_sets_combined_t<CV>(sigs, keys, key_off, n_sets, msg_blob, msg_off, group_off, n_groups, seed, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_multi_sets_combined_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set,
+                                        const void* d_msgs, size_t msg_len, size_t msg_stride, const uint64_t* group_off, size_t n_groups,
+                                        const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
+  int rc;
+  if ((rc = rlc_args_ok(group_off, n_groups, n_sets, seed))) return rc;
+  if (n_sets == 0) return 0;
+  if (!d_sigs || !d_key_off || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_multi_sets_combined_dev_t<CV>(d_sigs, d_keys, d_key_off, n_sets, max_set, d_msgs, msg_len, msg_stride, group_off, n_groups, seed,
+                                                       verdicts, gt_out, stream));
+} BGLS_ABI_GUARD
+
+int bgls_rlc_coefficients(const uint8_t* seed, size_t n, uint8_t* r_out) try {
+  if (n >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n must fit a uint32 (fewer than 2^28 coefficients)");
+  if (!seed || (n && !r_out)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n == 0) return 0;
+  return rlc_coefficients_t(seed, n, r_out);
+} BGLS_ABI_GUARD
+
 int bgls_verify_multi_hae_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* msg_blob,
                                const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) try {
   if (n_sets >= MAX_BATCH) return too_large();

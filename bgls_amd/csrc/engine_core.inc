@@ -102,7 +102,7 @@ int offsets_ok(const char* name, const uint64_t* off, size_t count, unsigned rul
 // workspace slots
 enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
        WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_HAE_NODES, WS_AMS_SIGNERS, WS_AMS_OFF, WS_AMS_BLOB, WS_AMS_PTS,
-       WS_AMS_SUMS, WS_AMS_AGG, WS_NUM };
+       WS_AMS_SUMS, WS_AMS_AGG, WS_RLC_SIGS, WS_RLC_SUMS, WS_RLC_OFF, WS_NUM };
 
 struct Ctx {
   std::mutex mu;
@@ -320,9 +320,10 @@ constexpr int miller_dbg() { return 0; }
 // of its pairs and its batched epilogue; ST_BB_KEYS by the batched Boneh-Boyen verification only (Engine::miller_bb: its Q_b = m_b g2 + U_b + r_b V_b)
 // ST_HAE_KEYS by the batched HAE multi-signatures only (bgls_verify_multi_hae_sets: the roots, the XOF expansion and the weighted main pass)
 // ST_AMS_MSGS by the batched accountable-subgroup multisignatures only (Engine::miller_ams: the assembly of the hash inputs)
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_NUM };
+// ST_RLC by the combined multi-signature check only (verify_sets_combined_run: the coefficients, k_rlc_pair, the per-group signature sums)
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_RLC, ST_NUM };
 const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys",
-                                         "hae_keys", "ams_msgs"};
+                                         "hae_keys", "ams_msgs", "rlc"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -347,12 +348,12 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs", "bgls:rlc"};
 
-struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on
+struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on; on = false: part of the caller's stage
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
-  Scope(Ctx& c_, hipStream_t st_, int stage_) : c(c_), st(st_), stage(stage_) {
-    if (c.prof) {
+  Scope(Ctx& c_, hipStream_t st_, int stage_, bool on = true) : c(c_), st(st_), stage(stage_) {
+    if (c.prof && on) {
       a = c.ev(); (void)hipEventRecord(a, st);
       if (roctx().push) { (void)roctx().push(STAGE_RANGES[stage]); ranged = true; }
     }
@@ -494,8 +495,14 @@ struct Engine {
   // launch sequence in its 60-pairing form (the 64-form's last four pairings join groups 0..3 of their block, so a group could straddle
   // two instances), a segmented reduce to one partial per instance, the batched epilogue (rest^h and the signature pair).  Writes
   // n_inst GT partials (bytes, no final exponentiation) to d_partials; d_iflags: n_inst words, zeroed by the caller.
+  // d_w16 != nullptr: pair i is (w_i H(m_i), pk_i) with 16-byte big-endian weights, as in miller_product.
+  // pre != nullptr (the combined multi-signature check): nothing is hashed or parsed here -- pre->g1s are the n resident G1 points of the
+  // pairs (already scaled; uncleared on BLS12-381) and pre->sigs the n_inst resident affine points that take the place of the -sigma_b;
+  // d_sigs, mv and d_w16 are not read.
+  struct PreScaled { const Aff<G1F>* g1s; const Aff<G1F>* sigs; };
   static int miller_product_batch(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
-                                  int check_dups, uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags) {
+                                  int check_dups, uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags, const uint8_t* d_w16 = nullptr,
+                                  const PreScaled* pre = nullptr) {
     const size_t n = inst_off[n_inst];
     if (n >= MAX_BATCH || n_inst >= MAX_BATCH) return too_large();
     constexpr bool raw = C::CURVE_ID == 1;                // BLS12-381: uncleared hash points, the cofactor applied per instance in the epilogue
@@ -545,8 +552,13 @@ struct Engine {
     void *d_tab, *g1s, *g1p, *keyp, *sigs, *epi;
     int rc;
     if ((rc = c.get(WS_BATCH_IDX, tab.size() * 8, &d_tab))) return rc;
-    if ((rc = c.get(WS_G1S, (n + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
-    if ((rc = c.get(WS_BATCH_SIGS, (n_inst + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
+    if (pre) {
+      g1s = (void*)pre->g1s;
+      sigs = (void*)pre->sigs;
+    } else {
+      if ((rc = c.get(WS_G1S, (n + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+      if ((rc = c.get(WS_BATCH_SIGS, (n_inst + 1) * sizeof(Aff<G1F>), &sigs))) return rc;
+    }
     if ((rc = c.get(WS_BATCH_EPI, (n_inst + 1) * 12 * sizeof(Fp2<C>), &epi))) return rc;
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
     const uint64_t* d_inst_off = (const uint64_t*)d_tab;
@@ -561,11 +573,12 @@ struct Engine {
       kl::dup_check_seg(st, mv, n, d_inst_off, (uint32_t)n_inst, (uint32_t*)table, (uint32_t)(cap - 1), d_iflags, dup_seed());
       HIPCHK(hipGetLastError());
     }
-    if (n) {
+    if (n && !pre) {
       Scope sc(c, st, ST_H2C);
       if ((rc = hash_to_g1(c, st, mv, n, (Aff<G1F>*)g1s, d_flags, raw))) return rc;
+      if (d_w16) kl::scale_g1_inplace<C>(st, (Aff<G1F>*)g1s, d_w16, n);
     }
-    kl::g1_parse<C>(st, d_sigs, n_inst, 1, (Aff<G1F>*)sigs, d_flags);                         // -sigma_b
+    if (!pre) kl::g1_parse<C>(st, d_sigs, n_inst, 1, (Aff<G1F>*)sigs, d_flags);               // -sigma_b
     void *pa, *pb;
     if ((rc = c.get(WS_F_A, (groups + max_out + 1) * 6 * sizeof(Fp2<C>), &pa))) return rc;
     if ((rc = c.get(WS_F_B, (max_out + 1) * 6 * sizeof(Fp2<C>), &pb))) return rc;
@@ -1075,8 +1088,9 @@ struct Engine {
   // nsets sums in one pass: set b = points d_off[b] .. d_off[b+1] (d_off: nsets + 1 offsets on the device, max_set = the
   // largest set); wire bytes of the nsets sums to d_out.  One main launch for all sets (P partials per set), then the
   // usual tree levels over the flat array of nsets * P partials -- P is a power of two, so no level pairs two sets.
+  // own_scope = false: the launches count towards the stage the caller has open.
   static int sum_sets(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, const uint64_t* d_off, size_t nsets, size_t max_set,
-                      uint8_t* d_out, uint32_t* d_flags) {
+                      uint8_t* d_out, uint32_t* d_flags, bool own_scope = true) {
     if (nsets == 0) return 0;
     // P partials (lane pairs / lanes) per set, a power of two.  The lane-pair kernel adds the 32 sums of a block itself and
     // leaves ONE partial per block, so a set of a few keys needs one block (P = 32) and no tree; the other kernels write one
@@ -1092,7 +1106,7 @@ struct Engine {
       return fail(BGLS_ERR_ARG, "too many key sets for one call (cut the batch: at most 2^30 blocks / 8 GiB of partial sums)");
     void *ja, *jb;
     int rc;
-    Scope sc(c, st, ST_SUM);
+    Scope sc(c, st, ST_SUM, own_scope);
     if ((rc = c.get(WS_JAC_A, (written + 1) * JB, &ja))) return rc;
     if ((rc = c.get(WS_JAC_B, (written / 2 + 2) * JB, &jb))) return rc;
     if (group == BGLS_G2 && sum_pairs()) kl::sumpairseg_main<C>(st, d_pts, d_off, nsets, (unsigned)P, ja, d_flags);

@@ -354,6 +354,136 @@ int verify_multi_sets_dev_t(const void* d_sigs, const void* d_keys, const void* 
   return verify_multi_sets_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
 }
 
+// ---- the combined check: many multi-signatures under one random linear combination per group (bgls_verify_multi_sets_combined) ----
+namespace host_blake2 { void xb_root(const uint8_t* data, size_t len, uint32_t xof_len, uint64_t h[8]); }
+
+// The rules of the groups of a combined call, checked before any device work: group_off == NULL means ONE group over all sets (n_groups
+// must be 1), else n_groups + 1 offsets into the sets, from 0, monotone, ending at n_sets.  The coefficients' XOF length 16 n_sets is a uint32.
+int rlc_args_ok(const uint64_t* group_off, size_t n_groups, size_t n_sets, const uint8_t* seed) {
+  if (n_sets >= MAX_BATCH || n_groups >= MAX_BATCH) return too_large();
+  if (n_sets >= HAE_MAX_SET) return fail(BGLS_ERR_ARG, "XOF length 16 n_sets must fit a uint32 (fewer than 2^28 sets)");
+  if (!seed) return fail(BGLS_ERR_ARG, "NULL seed");
+  if (!group_off) return n_groups == 1 ? 0 : fail(BGLS_ERR_ARG, "group_off == NULL means one group (n_groups must be 1)");
+  int rc;
+  if ((rc = offsets_ok("group_off", group_off, n_groups, OFF_FROM_ZERO))) return rc;
+  if (group_off[n_groups] != n_sets) return fail(BGLS_ERR_ARG, "group_off must end at n_sets");
+  return 0;
+}
+
+// root <- the BLAKE2Xb root of "bgls-rlc-v1" || seed || u64le(n) for an XOF of 16 n bytes (include/bgls_hip.h: bgls_rlc_coefficients)
+void rlc_root(const uint8_t* seed, size_t n, uint64_t root[8]) {
+  uint8_t in[11 + 32 + 8];
+  memcpy(in, "bgls-rlc-v1", 11);
+  memcpy(in + 11, seed, 32);
+  for (int j = 0; j < 8; ++j) in[43 + j] = (uint8_t)((uint64_t)n >> (8 * j));
+  host_blake2::xb_root(in, sizeof in, (uint32_t)(16 * n), root);
+}
+
+int rlc_coefficients_t(const uint8_t* seed, size_t n, uint8_t* r_out) {
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  int rc;
+  void *d_root, *d_r;
+  uint64_t root[8];
+  rlc_root(seed, n, root);
+  if ((rc = c.put(k.st, WS_HAE_ROOT, root, 64, &d_root))) return rc;
+  if ((rc = c.get(WS_HAE_T, n * 16, &d_r))) return rc;
+  kl::blake2x_expand(k.st, (const uint64_t*)d_root, (uint32_t)(16 * n), (uint8_t*)d_r);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(r_out, d_r, n * 16, hipMemcpyDeviceToHost, k.st));
+  HIPCHK(hipStreamSynchronize(k.st));                        // root[] is a stack buffer
+  for (size_t b = 0; b < n; ++b) r_out[16 * b + 15] |= 1;    // the lowest bit set: what k_rlc_pair multiplies by (rlc_scalar)
+  return 0;
+}
+
+// n_sets multi-signature sets under ONE check per group of consecutive sets: with r_b the coefficients of bgls_rlc_coefficients,
+// verdict g = [ e(-sum_b r_b sigma_b, g2) * prod_b e(r_b H(m_b), apk_b) == 1 ] over the sets b of group g.  Each stage once per call:
+// the key sums apk_b (Engine::sum_sets, wire bytes), one hashing pass, then under ST_RLC the coefficients (root on the host,
+// k_blake2x_expand), k_rlc_pair (r_b H_b in place, r_b sigma_b as wire bytes) and the segmented G1 sum per group with its negation;
+// Engine::miller_product_batch over the groups as instances on the pre-scaled points -- or, with one group, Engine::miller on the same
+// resident points, so that a single big group takes the unpadded 64-form -- and batch_verdicts_run's tail over n_groups items.
+// group_off: n_groups + 1 HOST offsets or nullptr (one group), already checked (rlc_args_ok); d_key_off: already checked.
+template <class C>
+int verify_sets_combined_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, const uint64_t* d_key_off, size_t n_sets, size_t max_set,
+                             MsgView mv, const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  typedef Aff<F1<C>> A1;
+  constexpr bool raw = C::CURVE_ID == 1;                     // BLS12-381: uncleared hash points, the cofactor applied per group in the epilogue
+  // host words on their way to WS_RLC_OFF in one copy: the XOF root, then the n_groups + 1 group offsets (alive until the tail has synchronised)
+  std::vector<uint64_t> tab(8 + n_groups + 1, 0);
+  rlc_root(seed, n_sets, tab.data());
+  uint64_t* goff = tab.data() + 8;
+  size_t max_group = 0;
+  for (size_t g = 0; g <= n_groups; ++g) goff[g] = group_off ? group_off[g] : (g ? n_sets : 0);
+  for (size_t g = 0; g < n_groups; ++g) max_group = goff[g + 1] - goff[g] > max_group ? goff[g + 1] - goff[g] : max_group;
+  return batch_verdicts_run<C>(c, st, n_groups, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t* d_iflags, uint32_t* d_flags) {
+    int rc;
+    void *d_apks, *g1s, *d_tab, *d_r, *d_rs, *d_sums, *sigs;
+    if ((rc = c.get(WS_SEG_KEYS, (n_sets + 1) * E::G2B, &d_apks))) return rc;
+    if ((rc = c.get(WS_G1S, (n_sets + 2) * sizeof(A1), &g1s))) return rc;
+    if ((rc = c.get(WS_HAE_T, n_sets * 16, &d_r))) return rc;
+    if ((rc = c.get(WS_RLC_SIGS, n_sets * E::G1B, &d_rs))) return rc;
+    if ((rc = c.get(WS_RLC_SUMS, (n_groups + 1) * E::G1B, &d_sums))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n_groups + 1) * sizeof(A1), &sigs))) return rc;
+    if (n_groups == 1) sigs = (A1*)g1s + n_sets;             // Engine::miller wants the signature point behind the hash points
+    if ((rc = E::sum_sets(c, st, BGLS_G2, d_keys, d_key_off, n_sets, max_set, (uint8_t*)d_apks, d_flags))) return rc;     // apk_b = AggregateKeys(set b)
+    {
+      Scope sc(c, st, ST_H2C);
+      if ((rc = E::hash_to_g1(c, st, mv, n_sets, (A1*)g1s, d_flags, raw))) return rc;
+    }
+    {
+      Scope sc(c, st, ST_RLC);
+      if ((rc = c.put(st, WS_RLC_OFF, tab.data(), tab.size() * 8, &d_tab))) return rc;
+      kl::blake2x_expand(st, (const uint64_t*)d_tab, (uint32_t)(16 * n_sets), (uint8_t*)d_r);
+      kl::rlc_pair<C>(st, (A1*)g1s, d_sigs, (const uint8_t*)d_r, n_sets, (uint8_t*)d_rs, d_flags);
+      HIPCHK(hipGetLastError());
+      if ((rc = E::sum_sets(c, st, BGLS_G1, (const uint8_t*)d_rs, (const uint64_t*)d_tab + 8, n_groups, max_group, (uint8_t*)d_sums, d_flags, false))) return rc;
+      kl::g1_parse<C>(st, (const uint8_t*)d_sums, n_groups, 1, (A1*)sigs, d_flags);                  // -sum_b r_b sigma_b
+      HIPCHK(hipGetLastError());
+    }
+    if (n_groups == 1) return E::miller(c, st, (const A1*)g1s, (const uint8_t*)d_apks, n_sets, (const A1*)sigs, d_part, d_flags, raw);
+    const typename E::PreScaled pre = {(const A1*)g1s, (const A1*)sigs};
+    return E::miller_product_batch(c, st, nullptr, (const uint8_t*)d_apks, MsgView{}, goff, n_groups, 0, d_part, d_iflags, d_flags, nullptr, &pre);
+  });
+}
+
+template <class C>
+int verify_multi_sets_combined_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets, const uint8_t* blob, const uint64_t* off,
+                                 const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  size_t max_set = 0;
+  MsgView mv;
+  void *d_sigs, *d_keys, *d_koff;
+  std::vector<uint64_t> rel;
+  if ((rc = offsets_ok("key_off", key_off, n_sets, 0, SIZE_MAX, &max_set))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = upload_key_sets(c, st, E::G2B, keys, key_off, n_sets, &d_keys, &d_koff, rel))) return rc;
+  if ((rc = upload_msgs(c, st, blob, off, n_sets, &mv))) return rc;
+  HIPCHK(hipStreamSynchronize(st));                       // rel goes out of scope
+  return verify_sets_combined_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_koff, n_sets, max_set, mv, group_off, n_groups,
+                                     seed, verdicts, gt_out);
+}
+
+template <class C>
+int verify_multi_sets_combined_dev_t(const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets, size_t max_set, const void* d_msgs,
+                                     size_t msg_len, size_t msg_stride, const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts,
+                                     uint8_t* gt_out, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  int rc;
+  std::vector<uint64_t> koff;
+  if ((rc = fetch_key_off(k.st, d_key_off, n_sets, max_set, false, d_keys, koff))) return rc;
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_sets_combined_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, group_off,
+                                     n_groups, seed, verdicts, gt_out);
+}
+
 // n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one set of launches: Engine::miller_bb (item n is the reference pair
 // (g1, g2)), then batch_verdicts_run's tail in its Boneh-Boyen form: verdicts[b] = (e(sigma_b, Q_b) == e(g1, g2)) byte for byte on the
 // device.  gt_out (nullable): the n GT elements.  An encoding failure anywhere (sigma, U, V) or a degenerate point step fails the whole call.

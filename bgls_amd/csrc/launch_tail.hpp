@@ -22,6 +22,9 @@ template <class C> void finalx_res(hipStream_t st, const uint8_t* partials, size
 template <class C> void scale_aff_g1x(hipStream_t st, const Aff<F1<C>>* g1_pts, const uint8_t* scalars, size_t n, uint8_t* out);
 template <class C> void scale_g1x(hipStream_t st, const uint8_t* pts, const uint8_t* scalars, const uint8_t* signs, size_t n, uint8_t* out, uint32_t* flags, int sbytes);
 
+// ---- k_rlc.hip: the combined check's per-set pair, hs[b] <- r_b hs[b] in place and out[b] <- r_b sigs[b] as wire bytes (r16: n x 16 bytes)
+template <class C> void rlc_pair(hipStream_t st, Aff<F1<C>>* hs, const uint8_t* sigs, const uint8_t* r16, size_t n, uint8_t* out, uint32_t* flags);
+
 // ---- k_millerlatx.hip: the narrow passes of the reduce stage on the two-wave 36-lane product (finalx.hpp)
 template <class C> void reduce_fx(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* out);
 // segmented form: out[G] = prod in[seg[2G] .. seg[2G] + seg[2G + 1]) for G < nout (an empty segment gives one)

@@ -1,6 +1,7 @@
 // C++ host-side mirror of the reference's Go package `bgls` on the hot path (bgls/bgls.go,
 // bgls/blsKosk.go): same function names and semantics, each verification = ONE batch C call.
 #pragma once
+#include <random>
 #include "curves.hpp"
 
 namespace bgls_go {   // "package bgls"; the name bgls:: is taken by the kernels' namespace
@@ -250,6 +251,76 @@ inline std::vector<bool> verifyMultiSignatures(const CurveSystem* curve, const s
     const size_t b = batch[i];
     out[b] = rc >= 0 ? verdicts[i] == 1 : verifyMultiSignature(curve, aggsigs[b], keys[b], msgs[b]);
   }
+  return out;
+}
+// "Are these multi-signatures all valid?" under one combined check per group of consecutive sets (bgls_verify_multi_sets_combined: one
+// final exponentiation per group).  group: sets per group, 0 = one group over all sets.  seed: 32 bytes from a CSPRNG drawn AFTER the
+// inputs are fixed (empty: drawn from std::random_device here).  One bool per group; ok (nullable) is cleared when the call could not
+// run -- lengths that differ, a set not made of this curve's points, an encoding or hashing error anywhere -- and the list is then all false.
+inline std::vector<bool> VerifyMultiSignaturesCombined(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                       const std::vector<Bytes>& msgs, size_t group = 0, Bytes seed = Bytes(), bool* ok = nullptr) {
+  const size_t n = aggsigs.size();
+  std::vector<uint64_t> goff(1, 0);
+  for (size_t at = 0; at < n;) goff.push_back(at = (group && at + group < n) ? at + group : n);
+  std::vector<bool> out(goff.size() - 1, false);
+  if (ok) *ok = false;
+  if (keys.size() != n || msgs.size() != n || (!seed.empty() && seed.size() != 32)) return out;
+  if (seed.empty()) {
+    std::random_device rd;
+    for (int i = 0; i < 32; ++i) seed.push_back((uint8_t)rd());
+  }
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> koff(1, 0), moff(1, 0);
+  for (size_t b = 0; b < n; ++b) {
+    Bytes one;
+    if (aggsigs[b].curve != curve || aggsigs[b].group != BGLS_G1 || !detail::g2_bytes(curve, keys[b], one)) return out;
+    sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+    kb.insert(kb.end(), one.begin(), one.end());
+    koff.push_back(koff.back() + keys[b].size());
+    blob.insert(blob.end(), msgs[b].begin(), msgs[b].end());
+    moff.push_back(blob.size());
+  }
+  if (ok) *ok = true;
+  if (n == 0) return out;
+  std::vector<uint8_t> verdicts(out.size(), 0);
+  const int rc = bgls_verify_multi_sets_combined(curve->id, sb.data(), kb.data(), koff.data(), n, blob.data(), moff.data(), goff.data(), out.size(), seed.data(),
+                                                 verdicts.data(), nullptr);
+  if (rc < 0 && ok) *ok = false;
+  for (size_t g = 0; g < out.size(); ++g) out[g] = rc >= 0 && verdicts[g] == 1;
+  return out;
+}
+// the same with 0x01 prepended to every message (bgls/blsKosk.go:117-120)
+inline std::vector<bool> KoskVerifyMultiSignaturesCombined(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                           const std::vector<Bytes>& msgs, size_t group = 0, Bytes seed = Bytes(), bool* ok = nullptr) {
+  std::vector<Bytes> pm;
+  for (const Bytes& m : msgs) {
+    Bytes one(1, 1);
+    one.insert(one.end(), m.begin(), m.end());
+    pm.push_back(one);
+  }
+  return VerifyMultiSignaturesCombined(curve, aggsigs, keys, pm, group, seed, ok);
+}
+// One bool per set at the combined check's cost where everything is valid: ONE combined call over groups of `group` sets, then ONE
+// verifyMultiSignatures call over only the sets of the rejected groups; the sets of accepted groups get true.  Where the combined call
+// cannot run, every set goes through verifyMultiSignatures.
+inline std::vector<bool> VerifyMultiSignaturesLocated(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& keys,
+                                                      const std::vector<Bytes>& msgs, size_t group = 64, Bytes seed = Bytes()) {
+  const size_t n = aggsigs.size();
+  bool ok = false;
+  const std::vector<bool> groups = VerifyMultiSignaturesCombined(curve, aggsigs, keys, msgs, group, seed, &ok);
+  if (!ok) return verifyMultiSignatures(curve, aggsigs, keys, msgs);
+  std::vector<bool> out(n, true);
+  std::vector<size_t> again;
+  for (size_t g = 0; g < groups.size(); ++g)
+    if (!groups[g])
+      for (size_t b = g * (group ? group : n); b < n && (group == 0 || b < (g + 1) * group); ++b) again.push_back(b);
+  if (again.empty()) return out;
+  std::vector<Point> s2;
+  std::vector<std::vector<Point>> k2;
+  std::vector<Bytes> m2;
+  for (size_t b : again) { s2.push_back(aggsigs[b]); k2.push_back(keys[b]); m2.push_back(msgs[b]); }
+  const std::vector<bool> v = verifyMultiSignatures(curve, s2, k2, m2);
+  for (size_t i = 0; i < again.size(); ++i) out[again[i]] = v[i];
   return out;
 }
 // B independent VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58) in ONE bgls_verify_multi_hae_sets call: one bool per set.  A set

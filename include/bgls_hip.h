@@ -131,6 +131,34 @@ int bgls_verify_multi_batch(int curve, const uint8_t* sigs, const uint8_t* keys,
  * Returns the number of accepted sets (>= 0) or < 0. */
 int bgls_verify_multi_sets(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
                            const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out);
+/* "Are these n_sets multi-signatures all valid?" under ONE combined check per group of consecutive sets: one final exponentiation per
+ * group instead of one per set.  Sets are described exactly as for bgls_verify_multi_sets.  With the coefficients r_b of
+ * bgls_rlc_coefficients(seed, n_sets) -- r_b belongs to the index b of the set in the call, whatever the grouping --
+ *   verdicts[g] = 1  iff  e(-sum_b r_b sigs[b], g2) * prod_b e(r_b H(m_b), apk_b) = 1  over the sets b of group g,  apk_b = sum of set b's keys.
+ * Groups: group_off holds n_groups + 1 HOST offsets into the sets, monotone, from 0, ending at n_sets; group_off == NULL with
+ * n_groups == 1 means one group holding all sets.  An empty group is accepted (the empty product).  A caller localises a failure by
+ * running the per-set call over the sets of the rejected groups only (the host mirrors' VerifyMultiSignaturesLocated does).
+ * gt_out: NULL or n_groups GT elements, the product above after the final exponentiation.
+ * THE CONTRACT.  A group whose sets bgls_verify_multi would all accept is always accepted.  A group holding a set that bgls_verify_multi
+ * rejects is rejected, except with probability about 2^-127 over a seed the adversary cannot predict (128-bit coefficients, one bit
+ * spent on keeping them non-zero).  The seed MUST be drawn from a CSPRNG AFTER the inputs are fixed and must never be reused where an
+ * adversary can see it first: whoever knows the coefficients in advance can shift two signatures by +r_2 D and -r_1 D and pass.
+ * (bgls_verify_multi_batch is this shape with every r_b = 1: it accepts such a shifted pair and cannot stand in for n_sets verdicts.)
+ * The equivalence is promised for signatures in G1 and keys in G2, i.e. Points constructed through bgls_check_points and its kin; for
+ * on-curve points outside the subgroups the verdict is unspecified (the call still does not fault).
+ * Errors as bgls_verify_multi_sets: a non-canonical or off-curve key or signature, a degenerate point step or an exhausted hash
+ * ANYWHERE fails the whole call (BGLS_ERR_ENCODING / BGLS_ERR_HASH) and leaves verdicts undefined; BGLS_ERR_NO_DEVICE without a device
+ * (no CPU fallback).  BGLS_ERR_ARG, checked before any device work: non-monotone offsets, group_off not from 0 or not ending at
+ * n_sets, group_off == NULL with n_groups != 1, a NULL seed, n_sets at or above 2^28 (the XOF length 16 n_sets is a uint32).
+ * n_sets == 0 returns 0.  Returns the number of accepted groups (>= 0) or < 0. */
+int bgls_verify_multi_sets_combined(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* key_off, size_t n_sets,
+                                    const uint8_t* msg_blob, const uint64_t* msg_off, const uint64_t* group_off, size_t n_groups,
+                                    const uint8_t seed[32], uint8_t* verdicts, uint8_t* gt_out);
+/* The coefficients of the combined check, defined here once: the XOF is BLAKE2Xb without a key (golang.org/x/crypto/blake2b NewXOF(16 n, nil))
+ * over "bgls-rlc-v1" || seed (32 bytes) || u64le(n) with output length 16 n; r_b is bytes [16 b, 16 b + 16) of its output, read
+ * big-endian, with the lowest bit set (never zero, at the cost of one bit of soundness).  r_out: n x 16 bytes, big-endian, the bit
+ * already set.  n < 2^28.  Returns 0 or < 0. */
+int bgls_rlc_coefficients(const uint8_t seed[32], size_t n, uint8_t* r_out);
 /* n independent bbsigs.Verify calls (bbsigs/bbsigs.go:68-73) in one set of launches: Boneh-Boyen signatures, item b is the signature
  * (sigmas[b], rs[b]) on the message scalar ms[b] under the key (U_b, V_b).
  * sigmas: n G1 points; rs, ms: n x 32-byte big-endian magnitudes; keys: n x (U || V), 2 G2 points each.
@@ -396,6 +424,11 @@ int bgls_verify_multi_batch_submit_dev(int curve, const void* d_sigs, const void
 int bgls_verify_multi_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
                                size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride,
                                uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_verify_multi_sets_combined with everything on the device: the arguments of bgls_verify_multi_sets_dev, then the HOST words
+ * group_off / n_groups / seed as in the host-pointer call. */
+int bgls_verify_multi_sets_combined_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
+                                        size_t max_set, const void* d_msgs, size_t msg_len, size_t msg_stride, const uint64_t* group_off,
+                                        size_t n_groups, const uint8_t seed[32], uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* bgls_verify_multi_hae_sets with everything on the device, shaped as bgls_verify_multi_sets_dev (d_key_off read back and checked,
  * every root on the device).  Same semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns. */
 int bgls_verify_multi_hae_sets_dev(int curve, const void* d_sigs, const void* d_keys, const void* d_key_off, size_t n_sets,
