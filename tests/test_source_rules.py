@@ -10,7 +10,7 @@ import os, re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bgls_amd", "csrc")
 FX_UNITS = ["k_millerlatx.hip", "k_finalx.hip", "k_sumtree.hip", "finalx.hpp", "miller_x.hpp", "k_millerx_bn.hip", "k_millerx_bls.hip",
-            "k_millerx64_bn.hip", "k_millerx64_bls.hip"]
+            "k_millerx64_bn.hip", "k_millerx64_bls.hip", "k_millersets.hip", "k_millerams.hip", "miller_group.hpp"]
 
 
 def closure(name, seen):
