@@ -32,6 +32,23 @@
 // addition step), consumer 66 per line + 84 / 6 per squaring (round 4: the squaring's cross terms in the Karatsuba form, rx.hpp).  Same line coefficients and the same product order as the
 // other kernels: the partial products are bit-identical to k_miller_ab64's.
 //
+//
+// XL, "xi on the line" (alt-bn128's 60-pairing block on the 29-bit form, MX<BN254W, 60>; -DMX_NO_XL for the A/B).  A fold's wrapped terms need a
+// factor xi = w^6:  c_j = sum_t L_t B_((j - sh t) mod 6) xi^[j < sh t],  sh = {0, 1, 3}.  Every other form keeps xi copies of the ACCUMULATOR: the
+// consumer -- the wave that arrives last at barrier A -- runs ux_mulxi in each of its seven publishes of a doubling step, on all six lanes, to
+// have xi e_5 (t = 1) and xi e_3..e_5 (t = 2) ready.  XL puts the factor on the LINE, xi (L_t B_k) = (xi L_t) B_k: the producer lane pair that
+// holds entries 1 and 2 in registers forms xi L_1 and xi L_2 (pair_mulxi_half: each lane its half of ux_mulxi, the partner's half by one quad
+// permute per limb) and hands FIVE entries over; a fold's lane reads xi L_t instead of L_t where its term wraps and the plain accumulator entry
+// from the second slot; the one publish of a doubling step whose next reader is the squaring -- which does need xi e_3..e_5 -- is the only one
+// left with a ux_mulxi.  Per block and doubling step: consumer 7 -> 1 ux_mulxi and 6 x 2 fewer half stores per lane of e_0..e_2, each producer
+// wave 2 half-ux_mulxi and 2 half stores more per lane and line.  Same field element in every coefficient at every step (tests/test_rx_xl.py).
+//   bounds   L_0, L_1 below 2.1 p, L_2 below 3.1 p (emit), xi L_1, xi L_2 tight, non-negative, below 3.001 p (pair_mulxi_half takes halves below
+//            3.3 p); accumulator entries below the folds' fixed point, 1.35 p (1.39 p with the xi on the accumulator: tools/gen_constants.py),
+//            so every operand is below RX_VBND p = 4 p, which RX_BIAS_D3 and the column budget are generated for -- both unchanged -- and the
+//            one ux_mulxi left sees values below its 3 p.
+//   LDS      40 800 bytes per block (static_assert: four blocks per CU): five entries per line, the second slots of e_0..e_2 dropped, the hash
+//            points' (-yP, xP) parked in the workspace (the P_IN_LDS == false path of the BLS12-381 64-form).  Map and conflict search: MX below.
+//
 // Replaces the n calls of CurveSystem.Pair behind PairingProduct: curves/curve.go:125-170, curves/altbn128.go:130-145,
 // curves/bls12_381.go:228-240.
 #pragma once
@@ -70,9 +87,21 @@ template <>
 struct MxForm<BN254> { typedef BN254W type; };
 #endif
 
-template <class C, int NP = 60>
+// XL ("xi on the line", alt-bn128's 60-form on the 29-bit number form only): the xi of a fold's wrapped terms is applied to the LINE by the producers,
+// once per line, instead of to the accumulator by every publish of the consumer -- xi (L_t B_k) = (xi L_t) B_k.  See the kernel's header comment and
+// the XL layout below.  -DMX_NO_XL keeps the kernel on the accumulator's xi copies (A/B measurements).
+template <class C, int NP>
+struct MxXlDefault { static constexpr bool value = false; };
+#ifndef MX_NO_XL
+template <>
+struct MxXlDefault<BN254W, 60> { static constexpr bool value = true; };
+#endif
+
+template <class C, int NP = 60, bool XL_ = MxXlDefault<C, NP>::value>
 struct MX {
   static_assert(NP == 60 || NP == 64, "pairings per block");
+  static constexpr bool XL = XL_;
+  static_assert(!XL || (NP == 60 && !rx_lazy<C> && C::TWIST_D && C::RX_NL <= 12), "XL: the 29-bit form's 60-pairing block, D-type twist");
   static constexpr int NL = C::RX_NL;
   static constexpr bool PACKED = (C::RX_NL % 4) != 0 && C::CURVE_ID == 1;   // BLS12-381: 14-dword halves back to back
   static constexpr int HS = PACKED ? NL : ((NL + 3) & ~3);                  // dwords per half: 12 / 14
@@ -80,8 +109,8 @@ struct MX {
   static constexpr int NLINES = NP == 64 ? 7 : 6;
   static constexpr int FOLD_UNROLL = (!rx_lazy<C> && NLINES % 3 == 0) ? 3 : 1;                   // the consumer's loop over a step's lines (k_miller_x60)
   static constexpr int KS = PACKED ? 2 * ES : ES;                           // accumulator entry stride: 24 / 56
-  static constexpr int WS = PACKED ? 368 : 176;                             // xi copies
-  static constexpr int GROUP_DW = PACKED ? (NP == 64 ? 940 : 844) : (NP == 64 ? 828 : 764);
+  static constexpr int WS = XL ? 112 : (PACKED ? 368 : 176);                // xi copies (XL: of e_3..e_5 only, so they start at WS + 3 KS)
+  static constexpr int GROUP_DW = XL ? 1020 : (PACKED ? (NP == 64 ? 940 : 844) : (NP == 64 ? 828 : 764));
   static constexpr int THREADS = 192;
   // accumulator entry (k, wrap) and line entry e = 3 m + t of a group, in dwords from the group's base
   static __device__ __forceinline__ int acc_off(int k, int wrap) { return k * KS + wrap * WS; }
@@ -90,7 +119,23 @@ struct MX {
     else return 320 + ES * e;
   }
   static_assert(!PACKED || (ES == 28 && 704 + 28 * (3 * NLINES - 13) <= GROUP_DW), "BLS12-381 line slots");
-  static_assert(PACKED || 320 + ES * 3 * NLINES <= GROUP_DW, "alt-bn128 line slots");
+  static_assert(PACKED || XL || 320 + ES * 3 * NLINES <= GROUP_DW, "alt-bn128 line slots");
+  // XL layout of a group (dwords; ES = 24, GROUP_DW = 1020 = 15 slots of 16 bytes mod 16, as the plain layout's 764):
+  //     0  plain e_0..e_5                      184  second slot of e_3..e_5 (acc_off(k, 1)): a COPY of the plain entry for the folds, xi e_k for the squaring
+  //   256  L_0 of lines 0..5 (yP-scaled)       400  L_1 (xP-scaled)        544 (+8 in groups 0..5)  xi L_1
+  //   696  xi L_2                              840  L_2 (P-free)           984 .. 1020 unused
+  // A fold's lane j reads entry t of the line as xi L_t where its term wraps (j < sh(t): lane 0 for t = 1, lanes 0..2 for t = 2) and the accumulator
+  // entry (j - sh(t)) mod 6 from the SECOND slot where it wraps: the accumulator fetches keep the plain layout's addresses, which are conflict-free.
+  // (One slot per accumulator entry cannot be: with group bases G g and entry slots A_k the four 16-lane groups of a ds_read_b128 force
+  // A_(k+1) - A_k = 10 G for all six k cyclically under the shifts 0, 1, 3, and 60 G is not 0 mod 16 for odd G.)  The line fetches: lanes of one
+  // 16-lane group now read L_t or xi L_t by j; tools/lds_conflicts.py (xl) searches the distance xi L_t - L_t mod 64 dwords: t = 2 any of 40..56
+  // (here -144 = 48), t = 1 NO single distance -- lanes of j = 0 meet lanes of j = 1, 2 in two 16-lane groups with different sets of g -- but one
+  // that steps by 8 dwords between two runs of groups: 24 in groups 0..5, 16 in groups 6..9 (here 152 / 144).  Every ds_read_b128 of a fold is
+  // conflict-free; the ninth limb's narrow read stays two-way conflicted as before.
+  static __device__ __forceinline__ int line_off_x(int m, int t, bool xi, bool glo) {
+    return t == 0 ? 256 + ES * m : (t == 1 ? (xi ? 544 + (glo ? 8 : 0) : 400) + ES * m : (xi ? 696 : 840) + ES * m);
+  }
+  static_assert(!XL || (ES == 24 && KS == 24 && WS + 3 * KS >= 6 * KS && WS + 6 * KS <= 256 && 840 + 6 * ES <= GROUP_DW), "XL line slots");
   // the hash points' coordinates (-yP, xP per pairing, read by both lanes of its pair at every step) live in LDS where a
   // quarter of a CU's 160 KB has room for them next to the groups, else in the lanes' global workspace (BLS12-381, NP = 64)
   static constexpr int PQ = 10 * GROUP_DW;            // [NP pairings][2] halves
@@ -103,6 +148,7 @@ struct MX {
   static constexpr int BLOCK_BYTES = (SEQ_DW + 16) * 4;
 #else
   static constexpr int BLOCK_BYTES = (10 * GROUP_DW + (P_IN_LDS ? NP * 2 * HS : 0)) * 4;
+  static_assert(!XL || (BLOCK_BYTES <= 40960 && !P_IN_LDS), "XL: four blocks per CU; the hash points' coordinates are parked in the workspace");
 #endif
   static constexpr int NPARK_Q = C::CURVE_ID == 0 ? 6 : 2;                  // xq yq [x1 y1 x2 y2]
   static constexpr int NPARK = NPARK_Q + (P_IN_LDS ? 0 : 2);                // ... nyP xP   (PS dwords each)
@@ -181,25 +227,45 @@ __device__ __forceinline__ void mx_st_half(int off, bool second, const Ux<C>& a)
 // PrepX<C> (prepared.hpp) for the prepared-key fold -- PACKED, HS, acc_off(k, wrap), line_off(e).  XI3: only the xi copies of coefficients 3..5 are
 // stored (nothing ever reads the others: every wrapped factor of a fold or a squaring is one of e_3, e_4, e_5); the Miller kernel stores all six
 // because its layout has the room and a predicated store costs what it saves.
-template <class C, class K, bool XI3 = false>
-__device__ __forceinline__ void mxk_publish(int gb, int j, const Ux2<C>& v, bool live) {
+// XL (MX's XL layout): the second slot of e_3..e_5 takes a copy of the plain value -- a fold reads its wrapped accumulator entries there, the xi is on
+// the line -- unless the next reader is the squaring (sq_next, wave-uniform): then, and only then, the xi multiple is formed.
+template <class C, class K, bool XI3 = false, bool XL = false>
+__device__ __forceinline__ void mxk_publish(int gb, int j, const Ux2<C>& v, bool live, bool sq_next = true) {
   if (live) {
     mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 0), false, v.c0);
     mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 0) + K::HS, true, v.c1);
-    const Ux2<C> x = ux_mulxi<C>(v);
-    if (!XI3 || j >= 3) {
-      mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1), false, x.c0);
-      mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1) + K::HS, true, x.c1);
+    if constexpr (XL) {
+      if (j >= 3) {
+        Ux2<C> x = v;
+        if (sq_next) x = ux_mulxi<C>(v);
+        mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1), false, x.c0);
+        mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1) + K::HS, true, x.c1);
+      }
+    } else {
+      const Ux2<C> x = ux_mulxi<C>(v);
+      if (!XI3 || j >= 3) {
+        mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1), false, x.c0);
+        mx_st_half<C, K::PACKED>(gb + K::acc_off(j, 1) + K::HS, true, x.c1);
+      }
     }
   }
   wave_sync();
 }
 template <class C, int NP>
-__device__ __forceinline__ void mx_publish(int gb, int j, const Ux2<C>& v, bool live) { mxk_publish<C, MX<C, NP>>(gb, j, v, live); }
+__device__ __forceinline__ void mx_publish(int gb, int j, const Ux2<C>& v, bool live, bool sq_next = false) {
+  mxk_publish<C, MX<C, NP>, false, MX<C, NP>::XL>(gb, j, v, live, sq_next);
+}
 // f <- f * line_m:  c_j = sum_t L[3m + t] * B[(j - sh[t]) mod 6] * xi^[sh[t] > j]
+// XL: the line entry of a wrapped term is its xi copy (glo: the group is one of 0..5, MX::line_off_x), the accumulator entry is plain in either slot
 template <class C, int NP>
-__device__ __forceinline__ Ux2<C> mx_fold(int gb, int m, int j) {
+__device__ __forceinline__ Ux2<C> mx_fold(int gb, int m, int j, bool glo = false) {
   typedef MX<C, NP> K;
+  if constexpr (K::XL) {
+    return ux_dot_k2p<C, 3, (C::RX_NL <= 10)>(
+        [&](int t, int h) { return mx_ld_half<C, K::PACKED>(gb + K::line_off_x(m, t, mxl_wraps<C>(j, t), glo) + h * K::HS, h != 0); },
+        [&](int t, int h) { return mx_ld_half<C, K::PACKED>(gb + K::acc_off(mxl_acc_k<C>(j, t), mxl_wraps<C>(j, t) ? 1 : 0) + h * K::HS, h != 0); });
+  } else {
+  (void)glo;
   // powers of w the line's three entries sit at: {0, 1, 3} (D-type twist) / {0, 2, 3} (M-type), as arithmetic on t: a table in
   // constant memory costs a scalar load and a wait for it in front of every operand fetch
   auto sh = [](int t) { return C::TWIST_D ? t + (t == 2 ? 1 : 0) : t + (t >= 1 ? 1 : 0); };
@@ -223,6 +289,7 @@ __device__ __forceinline__ Ux2<C> mx_fold(int gb, int m, int j) {
         k += 6 * wrap;
         return mx_ld_half<C, K::PACKED>(gb + K::acc_off(k, wrap) + h * K::HS, h != 0);
       });
+  }
 }
 // f <- f^2 with the symmetric terms merged (COOP_SQ_TAB)
 template <class C, class K>
@@ -523,12 +590,16 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     }
     const int rl_base = tg * K::GROUP_DW + (odd ? K::HS : 0);
     // the three line coefficients of a step: computed last in the step, held in registers over barrier A
-    Ux<C> e[3];
+    // XL: five -- e[3] = xi e[1], e[4] = xi e[2], the copies the folds' wrapped terms read (own halves, tight, non-negative, below 3.001 p)
+    Ux<C> e[K::XL ? 5 : 3];
     auto emit = [&](int which, const auto& v) __attribute__((always_inline)) {
       const int entry = which == 1 ? 1 : ((which == 0) == C::TWIST_D ? 0 : 2);     // D-type: c0 yP, c1 xP, c2;  M-type: c2, c1 xP, c0 yP
       if constexpr (rx_lazy<C>) e[entry] = sx_to_ux<C>(v);
       else if constexpr (std::is_same<std::decay_t<decltype(v)>, Sx<C, SX_T>>::value) e[entry] = sx_to_ux_p<C>(v);    // a reduction's output: + p, below 2.1 p
       else e[entry] = sx_to_ux_k<1, C>(v);              // the P-free coefficient, a difference of two reductions' outputs: + 2 p, below 3.1 p
+      if constexpr (K::XL) {
+        if (entry != 0) e[entry + 2] = pair_mulxi_half<C>(e[entry], odd);
+      }
     };
     int pstep = 0;                        // MX_EXP_FLAGS: line steps stored so far
     auto hand_over = [&]() __attribute__((always_inline)) {
@@ -540,6 +611,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
           e[0] = odd ? ux_zero<C>() : ux_load<C>(C::RX_ONE);
           e[1] = ux_zero<C>();
           e[2] = ux_zero<C>();
+          if constexpr (K::XL) { e[3] = ux_zero<C>(); e[4] = ux_zero<C>(); }
         }
       }
       mx_stamp<DBG>(srec, 16 + 4 * sstep);
@@ -550,9 +622,16 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
 #endif
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
       if (owner) {
-        mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m), odd, e[0]);
-        mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m + 1), odd, e[1]);
-        mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m + 2), odd, e[2]);
+        if constexpr (K::XL) {
+#pragma unroll
+          for (int t = 0; t < 3; ++t) mx_st_half<C, K::PACKED>(rl_base + K::line_off_x(m, t, false, tg < 6), odd, e[t]);
+          mx_st_half<C, K::PACKED>(rl_base + K::line_off_x(m, 1, true, tg < 6), odd, e[3]);
+          mx_st_half<C, K::PACKED>(rl_base + K::line_off_x(m, 2, true, tg < 6), odd, e[4]);
+        } else {
+          mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m), odd, e[0]);
+          mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m + 1), odd, e[1]);
+          mx_st_half<C, K::PACKED>(rl_base + K::line_off(3 * m + 2), odd, e[2]);
+        }
       }
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
 #ifdef MX_EXP_FLAGS
@@ -621,6 +700,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     const int g = cl % 10;
     const int j = cl / 10;
     const int gb = g * K::GROUP_DW;
+    const bool glo = g < 6;                                // XL: where the group's xi L_1 entries sit (MX::line_off_x)
     Ux2<C> fj;
     {
       const Ux<C> one = ux_load<C>(C::RX_ONE);
@@ -640,7 +720,8 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     int cstep = 0;                        // MX_EXP_FLAGS: line steps folded so far
     (void)cstep;
     if constexpr (!rx_lazy<C>) mx_sq_split(COOP_SQ_TAB[j], sq_d, sq_p);
-    auto fold_all = [&]() __attribute__((always_inline)) {
+    // sq_next (XL): the squaring reads this step's last publish, which therefore forms the xi copies of e_3..e_5 -- the only ux_mulxi of the step
+    auto fold_all = [&](bool sq_next) __attribute__((always_inline)) {
       if constexpr (DBG == 1) {
 #ifdef MX_EXP_FLAGS
         mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 2));
@@ -652,12 +733,12 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
       // (unrolled by two or three: 86.8 -> 87.2 ms)
 #pragma unroll K::FOLD_UNROLL
       for (int m = 0; m < K::NLINES; ++m) {
-        fj = mx_fold<C, NP>(gb, m, j);
+        fj = mx_fold<C, NP>(gb, m, j, glo);
 #ifdef MX_EXP_FLAGS
         if (m == 2) mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 1));                 // the fold's fetches are in LDS's queue ahead of this word
         if (m == K::NLINES - 1) mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 2));
 #endif
-        mx_publish<C, NP>(gb, j, fj, live);
+        mx_publish<C, NP>(gb, j, fj, live, sq_next && m == K::NLINES - 1);
       }
 #ifdef MX_EXP_FLAGS
       ++cstep;
@@ -698,7 +779,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
 #endif
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
       if constexpr (DBG == 4) ++sstep;
-      fold_all();
+      fold_all(C::LOOP_NAF[i] == 0 && i + 1 < C::LOOP_LEN);
       if (C::LOOP_NAF[i] != 0) {
         mx_stamp<DBG>(srec, 16 + 4 * sstep);
 #ifdef MX_EXP_FLAGS
@@ -713,7 +794,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
 #endif
         mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
         if constexpr (DBG == 4) ++sstep;
-        fold_all();
+        fold_all(i + 1 < C::LOOP_LEN);
       }
     }
     if constexpr (C::CURVE_ID == 0) {
@@ -732,7 +813,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
 #endif
         mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
         if constexpr (DBG == 4) ++sstep;
-        fold_all();
+        fold_all(false);
       }
     }
     if (live) {

@@ -352,6 +352,18 @@ BGLS_HD Ux2<C> ux_quasi(const Ux2<C>& a) {
 // Loops over the terms: the plain pass-1 loop and the pass-2 loop are unrolled (round 5, same-box A/B in tools/mb_x60.bin: BLS12-381 88.2 -> 86.5 ms,
 // alt-bn128 54.8 -> 54.4 ms per 2^20 pairings); the software-pipelined pass-1 loop stays rolled (unrolled it speeds the consumer alone up by 9 % and
 // the whole kernel not at all: the kernel's text is many times the instruction cache).
+// A line fold's terms (miller_x.hpp mx_fold):  c_j = sum_t L_t * B_((j - sh t) mod 6) * xi^[j < sh t].  mxl_sh: the power of w that entry t of a line
+// sits at, {0, 1, 3} on a D-type twist, {0, 2, 3} on an M-type; mxl_wraps: lane j's term t wraps (w^6 = xi); mxl_acc_k: the accumulator entry it takes.
+template <class C>
+BGLS_HD int mxl_sh(int t) { return C::TWIST_D ? t + (t == 2 ? 1 : 0) : t + (t >= 1 ? 1 : 0); }
+template <class C>
+BGLS_HD bool mxl_wraps(int j, int t) { return j < mxl_sh<C>(t); }
+template <class C>
+BGLS_HD int mxl_acc_k(int j, int t) {
+  const int k = j - mxl_sh<C>(t);
+  return k < 0 ? k + 6 : k;
+}
+
 template <class C, int NT, bool PF = false, class LA, class LB>
 BGLS_HD Ux2<C> ux_dot_k2p(LA&& lda, LB&& ldb) {
   constexpr int N = C::RX_NL;

@@ -59,6 +59,45 @@ RX_DEV Sx<C, LA> pair_swap_neg_even(const Sx<C, LA>& a, bool odd) {
   return r;
 }
 
+// Own half of xi * a on the lane pair (29-bit form, xi = 9 + i): the even lane 9 a0 - a1, the odd lane 9 a1 + a0, the partner's half by one quad
+// permute per limb.  It is the lane's half of ux_mulxi (rx.hpp), limb for limb: the quotient estimate off the top limbs, subtracted in the carry pass.
+// a: tight halves below 3.3 p -- the estimate is exact to 3 whatever the operand is, and its clamp at 31 needs 9 a0 - a1 + 4 p and 9 a1 + a0 below
+// 34 p; the line coefficients the producers hand over are below 2.1 p / 3.1 p.  Result: tight, non-negative, below 3.001 p, the same field element
+// as ux_mulxi's.  (The multiple of zero comes out as a multiple of p, not as zero limbs: the constant-1 line of an absent pairing gets its zero
+// copies from the caller.)
+template <class C>
+RX_DEV Ux<C> pair_mulxi_half(const Ux<C>& a, bool odd) {
+  static_assert(!rx_lazy<C>, "the lazy forms multiply by xi without a quotient (ux_mulxi)");
+  constexpr int T = C::RX_NL - 1;
+  constexpr float QI = 1.0f / (float)(C::RX_P[T] + 1u);
+  Ux<C> b;
+#pragma unroll
+  for (int i = 0; i <= T; ++i) b.v[i] = (u32)pair_swap1((i32)a.v[i]);
+#if RX_HOST_CHECK
+  for (int i = 0; i < T; ++i)
+    if (a.v[i] > C::RX_MASK) g_rx_overflow = 1;
+  if (3u * a.v[T] > 10u * C::RX_P[T]) g_rx_overflow = 1;
+#endif
+  const i32 s = (i32)((u32)C::XI_RE * a.v[T]) + (odd ? (i32)b.v[T] : 4 * (i32)C::RX_P[T] - (i32)b.v[T]);
+  i32 q = (i32)((float)s * QI) - 2;                       // as ux_mulxi's quot()
+  q = q < 0 ? 0 : q;
+  const u32 k = (u32)(32 - (q > 31 ? 31 : q));
+  Ux<C> r;
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < T; ++i) {
+    const u32 g = odd ? (u32)C::RX_XIG1[i] + b.v[i] : (u32)C::RX_XIG0[i] - b.v[i];
+    const u64 t = (u64)(u32)C::XI_RE * a.v[i] + (u64)k * C::RX_P[i] + (u64)g + c;
+    r.v[i] = (u32)t & C::RX_MASK;
+    c = t >> C::RX_W;
+  }
+  r.v[T] = (u32)((i32)((u32)C::XI_RE * a.v[T] + k * C::RX_P[T]) + (odd ? (i32)C::RX_XIG1[T] + (i32)b.v[T] : (i32)C::RX_XIG0[T] - (i32)b.v[T]) + (i32)c);
+#if RX_HOST_CHECK
+  if ((i32)r.v[T] < 0 || r.v[T] > 3u * C::RX_P[T] + 3u) g_rx_overflow = 1;
+#endif
+  return r;
+}
+
 // own half of a * b:   even lane  a0 b0 - a1 b1,   odd lane  a1 b0 + a0 b1.
 // Column factors: the own half of a and the partner's (sign-adjusted); row factors: limb i of b's even-lane half and of its
 // odd-lane half, fetched per row by quad permutes -- no select, and b's neighbour half never occupies NL registers.

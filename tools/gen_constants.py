@@ -235,6 +235,29 @@ def main():
                 # six term-equivalents x (a0 b1 + a1 b0): the FINAL totals of the squaring's cross pile, which rx.hpp's ux_sqr_dot forms as
                 # -(D + E) + sum (a0 + a1)(b0 + b1) mod 2^64 (Karatsuba; the sum alone would not fit on 14 limbs, it is never formed alone)
                 assert 12 * col[k] + red[k] + carry < (1 << 64), ("sqr cross pile", k)
+        if not lazy:
+            # The line folds' value bound on the narrow form (radix R' = 169 p: values must be SHOWN to stay small).  A reduction returns less than
+            # T / R' + p; the real part's columns total at most sum A_t B_t p^2 + BIAS, the imaginary part's 2 sum A_t B_t p^2, for operand bounds
+            # A_t p (line entry) and B_t p (accumulator entry).  Line entries: yP- and xP-scaled 2.1 p, P-free 3.1 p, xi copies 3.001 p.
+            #   xi on the accumulator (every form but XL):  wrapped term = L_t x (xi B) : A_t x 3.001
+            #   xi on the line (XL, miller_x.hpp):          wrapped term = (xi L_t) x B : 3.001 x F
+            # Lane 0 wraps t = 1 and t = 2, lanes 1, 2 wrap t = 2, lanes 3..5 nothing.  Up to 24 folds follow a squaring (whose output is below
+            # 2 p) before the next quasi-reduction, so the bound asked for is the iteration's fixed point F, from above and from below 2 p alike.
+            # F must stay below 3 p (ux_mulxi's precondition, XL: ahead of the squaring only), hence below VBND p = 4 p (what BIAS and the column
+            # budget above are generated for -- xi L_t and the second slot's plain copy are such operands, so neither changes) and from_ux_inl's 4 p.
+            bias_v = sum(b << (W * k) for k, b in enumerate(b3))
+            L0, L1, L2, XI = 2.1, 2.1, 3.1, 3.001
+            def fold_fixed_point(xl):
+                F = float(VBND)
+                for _ in range(64):
+                    if xl:
+                        s = max(L0 * F + XI * F + XI * F, (L0 + L1) * F + XI * F, (L0 + L1 + L2) * F)
+                    else:
+                        s = max(L0 * F + (L1 + L2) * XI, (L0 + L1) * F + L2 * XI, (L0 + L1 + L2) * F)
+                    F = max((s * p * p + bias_v) / (Rp * p), 2 * s * p / Rp) + 1
+                return F
+            f_acc, f_xl = fold_fixed_point(False), fold_fixed_point(True)
+            assert f_acc < 1.6 and f_xl < 1.6, (f_acc, f_xl)          # 1.39 p / 1.35 p on alt-bn128: far inside ux_mulxi's 3 p
         o += "  static constexpr uint64_t RX_BIAS_D3[%d] = {%s};\n" % (2 * N, ", ".join("0x%xull" % b for b in b3))
         o += "  static constexpr uint64_t RX_BIAS_S6[%d] = {%s};\n" % (2 * N, ", ".join("0x%xull" % b for b in b6))
         if b2x3 is not None:

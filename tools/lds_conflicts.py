@@ -7,6 +7,7 @@ distinct address on a busy bank of a group costs one more LDS cycle.  Reports th
 Miller step of the consumer (squaring + six line folds), which is what SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE measures.
 
 usage: lds_conflicts.py [search]
+       lds_conflicts.py xl [search]      the XL form of alt-bn128's 60-pairing block
 """
 import itertools
 import sys
@@ -131,7 +132,73 @@ def report(name, lay):
     return e / (b + e)
 
 
+# ---- the XL form of alt-bn128's 60-pairing block (miller_x.hpp MX<BN254W, 60, true>): the xi of a fold's wrapped terms sits on the LINE.
+# Lane j of a group reads entry t of a line as xi L_t where j < sh(t) and as L_t elsewhere, so the lanes of one 16-lane group no longer share
+# one line address per group; the accumulator entry comes from the second slot where the term wraps, which keeps the plain layout's addresses.
+XL_NL, XL_HS, XL_ES = 9, 12, 24
+XL_SH = (0, 1, 3)
+
+
+def xl_cycles(fn):
+    """extra LDS cycles of one operand fetch (both halves), split into the 16-byte reads and the ninth limb's narrow read"""
+    global MAPPING
+    keep, MAPPING = MAPPING, "jmajor"
+    wide = narrow = 0
+    for h in (0, 1):
+        for off, w in half_reads(XL_NL, 0):
+            addrs = [0] * 64
+            for lane, g, j in lanes():
+                addrs[lane] = fn(g, j, h) + off
+            b, e = cycles(addrs, w)
+            if w == 4:
+                wide += e
+            else:
+                narrow += e
+    MAPPING = keep
+    return wide, narrow
+
+
+def xl_line(group_dw, t, dist_lo, dist_hi, brk):
+    """entry t of a line: L_t at a fixed offset, xi L_t at dist_lo (groups below brk) / dist_hi dwords from it"""
+    return lambda g, j, h: g * group_dw + 4096 + XL_HS * h + ((dist_lo if g < brk else dist_hi) if j < XL_SH[t] else 0)
+
+
+def xl_acc(group_dw, ws, t, second_slot):
+    def fn(g, j, h):
+        k = j - XL_SH[t]
+        wrap = 1 if k < 0 else 0
+        return g * group_dw + XL_ES * (k + 6 * wrap) + (ws * wrap if second_slot else 0) + XL_HS * h
+    return fn
+
+
+def xl_report():
+    gd, ws = 1020, 112                     # MX<BN254W, 60, true>: GROUP_DW, WS; xi L_1 - L_1 = 152 / 144 (groups 0..5 / 6..9), xi L_2 - L_2 = -144
+    print("XL layout, GROUP_DW %d (block %d B): extra LDS cycles per operand fetch (16-byte reads, narrow read)" % (gd, 10 * gd * 4))
+    for t in range(3):
+        print("  t = %d   line %s   accumulator, second slot %s   accumulator, ONE slot per entry %s" %
+              (t, xl_cycles(xl_line(gd, t, 152 if t == 1 else -144, 144 if t == 1 else -144, 6)), xl_cycles(xl_acc(gd, ws, t, True)),
+               xl_cycles(xl_acc(gd, ws, t, False))))
+    return [xl_cycles(xl_line(gd, t, 152 if t == 1 else -144, 144 if t == 1 else -144, 6))[0] for t in range(3)] + \
+           [xl_cycles(xl_acc(gd, ws, t, True))[0] for t in range(3)]
+
+
+def xl_search():
+    gd = 1020
+    for t in (1, 2):
+        one = [d for d in range(0, 64, 4) if xl_cycles(xl_line(gd, t, d + 64, d + 64, 0))[0] == 0]
+        print("  t = %d: distances xi L_t - L_t (mod 64 dwords) with conflict-free 16-byte reads: %s" % (t, one or "none"))
+        if not one:
+            two = [(brk, lo, hi) for brk in range(1, 10) for lo in range(0, 64, 4) for hi in range(0, 64, 4)
+                   if xl_cycles(xl_line(gd, t, lo + 64, hi + 64, brk))[0] == 0]
+            print("         with one step between two runs of groups (groups below, distance there, distance above): %s" % two)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "xl":
+        assert not any(xl_report()), "XL layout: a 16-byte fold fetch is conflicted"
+        if len(sys.argv) > 2 and sys.argv[2] == "search":
+            xl_search()
+        sys.exit(0)
     for nl, twist_d, cname in ((10, True, "alt-bn128"), (14, False, "BLS12-381")):
         hs = (nl + 3) & ~3
         report("%s round 3 (padded halves, +4)" % cname, Layout(nl, 2 * hs, hs, 30 * 2 * hs + 4, twist_d))
