@@ -458,7 +458,7 @@ static void final_exp(fp12* r, const fp12* in) {
 
 /* ------------------------------------------------------------------ hash to G1 */
 #if CURVE_IS_BN
-static int hash_to_g1(g1a* out, const uint8_t* msg, size_t len) {   /* tryAndIncrementEvm */
+static int h2c_tries(g1a* out, const uint8_t* msg, size_t len) {   /* tryAndIncrementEvm; returns the number of counters tried, 0 = none of the 256 accepts */
   uint8_t* buf = (uint8_t*)malloc(len + 1); uint8_t h[32];
   memcpy(buf + 1, msg, len);
   for (int c = 0; c < 256; c++) {
@@ -470,11 +470,12 @@ static int hash_to_g1(g1a* out, const uint8_t* msg, size_t len) {   /* tryAndInc
     if (fp_eq(&t, &y2)) {
       buf[0] = 0xFF; keccak256_legacy(buf, len + 1, h);
       if (h[31] & 1) fp_neg(&r, &r);
-      out->x = x; out->y = r; out->inf = 0; free(buf); return 1;
+      out->x = x; out->y = r; out->inf = 0; free(buf); return c + 1;
     }
   }
   free(buf); return 0;
 }
+static int hash_to_g1(g1a* out, const uint8_t* msg, size_t len) { return h2c_tries(out, msg, len) != 0; }
 #else
 static int plain_parity(const fp* a_mont) {          /* parity(): a > q - a, curves/hash.go:169-172 */
   fp a, d; fp_from_mont(&a, a_mont); raw_sub(d.v, PMOD, a.v);
@@ -554,6 +555,10 @@ static int run_pairs(fp12* out, const uint8_t* g1s, const uint8_t* g2s, const ui
 
 /* ------------------------------------------------------------------ exports */
 int FN(hash_to_g1)(const uint8_t* msg, size_t len, uint8_t* out) { g1a p; if (!hash_to_g1(&p, msg, len)) return -3; g1_write(out, &p); return 0; }
+#if CURVE_IS_BN
+/* the try count of the loop above (first accepting counter + 1; 0: none accepts), for mining messages that need many tries (tests/golden/make_h2c_deep.py) */
+int FN(h2c_tries)(const uint8_t* msg, size_t len) { g1a p; return h2c_tries(&p, msg, len); }
+#endif
 int FN(miller)(const uint8_t* g1, const uint8_t* g2, uint8_t* out) {
   g1a P; g2a Q; fp12 f; if (!g1_read(&P, g1) || !g2_read(&Q, g2)) return -2; miller(&f, &P, &Q); gt_write(out, &f); return 0;
 }

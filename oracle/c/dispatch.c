@@ -12,6 +12,8 @@
 DECL(bn) DECL(bls)
 #define D(name, ...) (curve == 0 ? bn_##name(__VA_ARGS__) : curve == 1 ? bls_##name(__VA_ARGS__) : -1)
 int oracle_hash_to_g1(int curve, const uint8_t* m, size_t l, uint8_t* o) { return D(hash_to_g1, m, l, o); }
+int bn_h2c_tries(const uint8_t*, size_t);
+int oracle_bn_h2c_tries(const uint8_t* m, size_t l) { return bn_h2c_tries(m, l); }
 int oracle_miller(int curve, const uint8_t* a, const uint8_t* b, uint8_t* o) { return D(miller, a, b, o); }
 int oracle_final_exp(int curve, const uint8_t* a, uint8_t* o) { return D(final_exp, a, o); }
 int oracle_pairing_product(int curve, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* o, int threads, int faithful) { return D(pairing_product, a, b, n, o, threads, faithful); }

@@ -42,6 +42,11 @@ def hash_to_g1(curve, msg):
     return bytes(o)
 
 
+def bn_h2c_tries(msg):
+    """alt-bn128 try-and-increment: the number of counters tried (first accepting counter + 1; 0 when none of the 256 accepts)"""
+    return lib().oracle_bn_h2c_tries(_b(msg), ctypes.c_size_t(len(msg)))
+
+
 def miller(curve, g1, g2):
     o = (ctypes.c_uint8 * (12 * FP[curve]))()
     assert lib().oracle_miller(curve, _b(g1), _b(g2), o) == 0
