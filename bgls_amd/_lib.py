@@ -31,6 +31,14 @@ SIGNATURES = {
     "bgls_verify_aggregate": (ci, [ci, u8p, u8p, u8p, u64p, sz, ci]),
     "bgls_verify_aggregate_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci, u8p, u8p]),
     "bgls_verify_aggregate_batch_dev": (ci, [ci, vp, vp, u64p, sz, vp, sz, sz, ci, u8p, u8p, vp]),
+    "bgls_hash_to_g1_keyed": (ci, [ci, ci, u8p, u8p, u64p, sz, u8p]),
+    "bgls_verify_aggregate_distinct": (ci, [ci, u8p, u8p, u8p, u64p, sz]),
+    "bgls_verify_aggregate_distinct_h": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, u8p]),
+    "bgls_verify_aggregate_distinct_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p]),
+    "bgls_verify_aggregate_distinct_batch_dev": (ci, [ci, vp, vp, u64p, sz, vp, sz, sz, u8p, u8p, vp]),
+    "bgls_verify_single_distinct_batch": (ci, [ci, u8p, u8p, u8p, u64p, sz, u8p, u8p]),
+    "bgls_verify_single_distinct_batch_dev": (ci, [ci, vp, vp, sz, vp, sz, sz, u8p, u8p, vp]),
+    "bgls_check_authentication_batch": (ci, [ci, u8p, u8p, sz, u8p, u8p]),
     "bgls_verify_multi": (ci, [ci, u8p, u8p, sz, u8p, sz]),
     "bgls_verify_multi_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci]),
     "bgls_verify_multi_sets": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, u8p, u8p]),

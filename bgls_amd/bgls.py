@@ -464,14 +464,96 @@ def DistinctMsgSign(curve, sk, msg):                          # bgls/blsDistinct
     return Sign(curve, sk, LoadPublicKey(curve, sk).MarshalUncompressed() + bytes(msg))
 
 
+def _is_point(p, curve, group):
+    return isinstance(p, Point) and p.curve is curve and p.group == group
+
+
+def _verify_single_keyed(curve, sigs, pubkeys, msgs):
+    """One bgls_verify_single_distinct_batch (msgs a list) or bgls_check_authentication_batch (msgs None) call for the items made of
+    Points of this curve; a nil or foreign point is False, as the single path says.  A call that fails as a whole (an encoding or hashing
+    error somewhere in the batch) is settled item by item through batches of one."""
+    n = len(sigs)
+    if n != len(pubkeys) or (msgs is not None and n != len(msgs)):
+        raise ValueError("sigs, pubkeys and msgs differ in length")
+    out = [False] * n
+    batch = [b for b in range(n) if _is_point(sigs[b], curve, G1) and _is_point(pubkeys[b], curve, G2)]
+    if not batch:
+        return out
+
+    def call(items):
+        verdicts = (ctypes.c_uint8 * len(items))()
+        sg, ks = _lib.buf(b"".join(sigs[b].raw for b in items)), _lib.buf(b"".join(pubkeys[b].raw for b in items))
+        if msgs is None:
+            rc = _lib.load().bgls_check_authentication_batch(curve.id, ks, sg, len(items), verdicts, None)
+        else:
+            ms = [bytes(msgs[b]) for b in items]
+            rc = _lib.load().bgls_verify_single_distinct_batch(curve.id, sg, ks, _lib.buf(b"".join(ms)), _offsets(ms), len(items), verdicts, None)
+        return rc, verdicts
+
+    rc, verdicts = call(batch)
+    for i, b in enumerate(batch):
+        if rc >= 0:
+            out[b] = verdicts[i] == 1
+        elif len(batch) > 1:
+            one_rc, one = call([b])
+            out[b] = one_rc >= 0 and one[0] == 1
+    return out
+
+
 def DistinctMsgVerifySingleSignature(curve, sig, pubkey, msg):   # bgls/blsDistinctMessage.go:37-40
-    return VerifySingleSignature(curve, sig, pubkey, pubkey.MarshalUncompressed() + bytes(msg))
+    return _verify_single_keyed(curve, [sig], [pubkey], [msg])[0]
+
+
+def DistinctMsgVerifySingleSignatures(curve, sigs, pubkeys, msgs):
+    """len(sigs) independent DistinctMsgVerifySingleSignature calls in one batch: a list of bools.  The key bytes are put in front of
+    every message on the device."""
+    return _verify_single_keyed(curve, sigs, pubkeys, msgs)
 
 
 def DistinctMsgVerifyAggregateSignature(curve, aggsig, keys, msgs):   # bgls/blsDistinctMessage.go:45-57
+    """keys: a list of G2 Points or a KeySet.  The key bytes are put in front of every message on the device (from the resident wire
+    bytes of a KeySet); there is no duplicate rule."""
     if len(keys) != len(msgs):
         return False
-    return _verify_agg(curve, aggsig, keys, [k.MarshalUncompressed() + bytes(m) for k, m in zip(keys, msgs)], True)
+    if not _is_point(aggsig, curve, G1):
+        return False
+    ms = [bytes(m) for m in msgs]
+    if isinstance(keys, KeySet):
+        if keys.curve is not curve:
+            return False
+        return _lib.load().bgls_verify_aggregate_distinct_h(keys.handle, _lib.buf(aggsig.raw), _lib.buf(b"".join(ms)), _offsets(ms), len(ms), None) == 1
+    if not all(_is_point(k, curve, G2) for k in keys):
+        return False
+    return _lib.load().bgls_verify_aggregate_distinct(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), _lib.buf(b"".join(ms)),
+                                                      _offsets(ms), len(ms)) == 1
+
+
+def DistinctMsgVerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
+    """len(aggsigs) independent DistinctMsgVerifyAggregateSignature calls in one batch (bgls_verify_aggregate_distinct_batch): a list of
+    bools, one per instance.  An instance that is not made of Points of this curve (mismatched lengths, a foreign point, a KeySet) gets
+    what the single call says about it; a call that fails as a whole is settled instance by instance."""
+    if not (len(aggsigs) == len(keys_per_instance) == len(msgs_per_instance)):
+        raise ValueError("aggsigs, keys_per_instance and msgs_per_instance differ in length")
+    out = [False] * len(aggsigs)
+    batch = []
+    for b, (sig, keys, msgs) in enumerate(zip(aggsigs, keys_per_instance, msgs_per_instance)):
+        if _is_point(sig, curve, G1) and not isinstance(keys, KeySet) and len(keys) == len(msgs) and all(_is_point(k, curve, G2) for k in keys):
+            batch.append(b)
+        else:
+            out[b] = DistinctMsgVerifyAggregateSignature(curve, sig, keys, msgs)
+    if not batch:
+        return out
+    inst_off = (ctypes.c_uint64 * (len(batch) + 1))()
+    for i, b in enumerate(batch):
+        inst_off[i + 1] = inst_off[i] + len(keys_per_instance[b])
+    msgs = [bytes(m) for b in batch for m in msgs_per_instance[b]]
+    verdicts = (ctypes.c_uint8 * len(batch))()
+    rc = _lib.load().bgls_verify_aggregate_distinct_batch(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
+                                                          _lib.buf(b"".join(k.raw for b in batch for k in keys_per_instance[b])), inst_off, len(batch),
+                                                          _lib.buf(b"".join(msgs)), _offsets(msgs), verdicts, None)
+    for i, b in enumerate(batch):
+        out[b] = verdicts[i] == 1 if rc >= 0 else DistinctMsgVerifyAggregateSignature(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b])
+    return out
 
 
 def Authenticate(curve, sk):                                  # bgls/blsKosk.go:44-55: a signature on the marshalled key
@@ -479,7 +561,13 @@ def Authenticate(curve, sk):                                  # bgls/blsKosk.go:
 
 
 def CheckAuthentication(curve, pubkey, authentication):      # bgls/blsKosk.go:59-69
-    return VerifySingleSignature(curve, authentication, pubkey, pubkey.Marshal())
+    return _verify_single_keyed(curve, [authentication], [pubkey], None)[0]
+
+
+def CheckAuthentications(curve, pubkeys, authentications):
+    """len(pubkeys) independent CheckAuthentication calls in one batch (bgls_check_authentication_batch): a list of bools.  The compressed
+    keys that the proofs of possession sign are made on the device."""
+    return _verify_single_keyed(curve, authentications, pubkeys, None)
 
 
 def KoskVerifyBatchMultiSignatureStepwise(curve, aggsigs, pubkeys, msgs):    # bgls/blsKosk.go:126-133, call by call as the reference writes it

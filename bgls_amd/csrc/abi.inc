@@ -50,6 +50,78 @@ int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d
   DISPATCH(curve, verify_aggregate_batch_dev_t<CV>(d_sigs, d_keys, inst_off, n_inst, d_msgs, msg_len, msg_stride, allow_duplicates, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+// ---- distinct messages (bgls/blsDistinctMessage.go) and proofs of possession (bgls/blsKosk.go:59-69): the hash inputs are built on the device
+int bgls_verify_aggregate_distinct(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (!sig || !msg_off || (n && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (msg_off[n] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_aggregate_t<CV>(sig, keys, msg_blob, msg_off, n, 1, true));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_distinct_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* msg_blob,
+                                         const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n_inst >= MAX_BATCH) return too_large();
+  if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("inst_off", inst_off, n_inst, OFF_FROM_ZERO | OFF_TOTAL))) return rc;
+  if (n_inst == 0) return 0;
+  if (!sigs || !verdicts || !msg_off || (inst_off[n_inst] && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if ((rc = offsets_ok("msg_off", msg_off, inst_off[n_inst], 0))) return rc;
+  if (msg_off[inst_off[n_inst]] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_aggregate_batch_t<CV>(sigs, keys, inst_off, n_inst, msg_blob, msg_off, 1, verdicts, gt_out, true));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_distinct_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs,
+                                             size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
+  if (n_inst >= MAX_BATCH) return too_large();
+  if (!inst_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("inst_off", inst_off, n_inst, OFF_FROM_ZERO | OFF_TOTAL))) return rc;
+  if (n_inst == 0) return 0;
+  if (!d_sigs || !verdicts || (inst_off[n_inst] && (!d_keys || (msg_len && !d_msgs)))) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_aggregate_batch_dev_t<CV>(d_sigs, d_keys, inst_off, n_inst, d_msgs, msg_len, msg_stride, 1, verdicts, gt_out, stream, true));
+} BGLS_ABI_GUARD
+
+int bgls_verify_single_distinct_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n,
+                                      uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (!msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (n == 0) return 0;
+  if (!sigs || !keys || !verdicts || (msg_off[n] > msg_off[0] && !msg_blob)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_single_keyed_t<CV>(BGLS_KEYED_PREFIX, sigs, keys, msg_blob, msg_off, n, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_single_distinct_batch_dev(int curve, const void* d_sigs, const void* d_keys, size_t n, const void* d_msgs, size_t msg_len, size_t msg_stride,
+                                          uint8_t* verdicts, uint8_t* gt_out, void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!d_sigs || !d_keys || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_single_distinct_dev_t<CV>(d_sigs, d_keys, n, d_msgs, msg_len, msg_stride, verdicts, gt_out, stream));
+} BGLS_ABI_GUARD
+
+int bgls_check_authentication_batch(int curve, const uint8_t* keys, const uint8_t* auths, size_t n, uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!keys || !auths || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, verify_single_keyed_t<CV>(BGLS_KEYED_POP, auths, keys, nullptr, nullptr, n, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_hash_to_g1_keyed(int curve, int mode, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint8_t* g1_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (mode != BGLS_KEYED_PREFIX && mode != BGLS_KEYED_POP) return fail(BGLS_ERR_ARG, "mode must be BGLS_KEYED_PREFIX or BGLS_KEYED_POP");
+  if (n && (!keys || !g1_out || (mode == BGLS_KEYED_PREFIX && !msg_off))) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n && mode == BGLS_KEYED_PREFIX) {
+    int rc;
+    if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+    if (msg_off[n] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  }
+  DISPATCH(curve, hash_to_g1_keyed_t<CV>(mode, keys, msg_blob, msg_off, n, g1_out));
+} BGLS_ABI_GUARD
+
 int bgls_verify_multi(int curve, const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) try {
   if (n >= MAX_BATCH) return too_large();
   if (!sig || (n && !keys) || (msg_len && !msg)) return fail(BGLS_ERR_ARG, "NULL argument");
@@ -315,6 +387,18 @@ int bgls_verify_aggregate_h_gt(bgls_keys_t handle, const uint8_t* sig, const uin
   if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
   if (!sig || !msg_off || !gt_out) return fail(BGLS_ERR_ARG, "NULL argument");
   DISPATCH(ks->curve, verify_aggregate_h_t<CV>(*ks, sig, msg_blob, msg_off, n, allow_duplicates, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_distinct_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  auto ks = keyset(handle);
+  if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
+  if (!sig || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n != ks->n) return fail(BGLS_ERR_ARG, "message count differs from the key set's size");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (msg_off[n] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(ks->curve, verify_aggregate_h_t<CV>(*ks, sig, msg_blob, msg_off, n, 1, gt_out, true));
 } BGLS_ABI_GUARD
 
 int bgls_rccl_available(void) try { return rccl().ok ? 1 : 0; } BGLS_ABI_GUARD

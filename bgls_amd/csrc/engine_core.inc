@@ -102,7 +102,7 @@ int offsets_ok(const char* name, const uint64_t* off, size_t count, unsigned rul
 // workspace slots
 enum { WS_G1S = 0, WS_F_A, WS_F_B, WS_FLAGS, WS_TABLE, WS_IN_A, WS_IN_B, WS_IN_C, WS_IN_D, WS_OUT, WS_JAC_A, WS_JAC_B, WS_PART, WS_TMP, WS_TMP2, WS_H2C_LIST, WS_H2C_CNT, WS_H2C_PTS, WS_H2C_KIND, WS_HAE_ROOT, WS_HAE_T, WS_HAE_KEYS, WS_HAE_APK, WS_HAE_SIGN, WS_FLAGS2, WS_GEN_TMP, WS_LINES, WS_SUMJ, WS_QP, WS_MSM_AFF, WS_MSM_CNT, WS_MSM_START, WS_MSM_LIST, WS_SEG_OFF, WS_SEG_KEYS, WS_EPI, WS_TREE_S, WS_TREE_T,
        WS_BATCH_IDX, WS_BATCH_G1, WS_BATCH_KEYS, WS_BATCH_SIGS, WS_BATCH_EPI, WS_BATCH_RES, WS_HAE_NODES, WS_AMS_SIGNERS, WS_AMS_OFF, WS_AMS_BLOB, WS_AMS_PTS,
-       WS_AMS_SUMS, WS_AMS_AGG, WS_RLC_SIGS, WS_RLC_SUMS, WS_RLC_OFF, WS_NUM };
+       WS_AMS_SUMS, WS_AMS_AGG, WS_RLC_SIGS, WS_RLC_SUMS, WS_RLC_OFF, WS_KEYED_BLOB, WS_KEYED_OFF, WS_NUM };
 
 struct Ctx {
   std::mutex mu;
@@ -321,9 +321,11 @@ constexpr int miller_dbg() { return 0; }
 // ST_HAE_KEYS by the batched HAE multi-signatures only (bgls_verify_multi_hae_sets: the roots, the XOF expansion and the weighted main pass)
 // ST_AMS_MSGS by the batched accountable-subgroup multisignatures only (Engine::miller_ams: the assembly of the hash inputs)
 // ST_RLC by the combined multi-signature check only (verify_sets_combined_run: the coefficients, k_rlc_pair, the per-group signature sums)
-enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_RLC, ST_NUM };
+// ST_KEY_MSGS by the distinct-message and authentication checks only (Engine::key_msgs: the hash inputs built from the keys on the device)
+enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_KEY_MSGS, ST_RLC,
+       ST_NUM };
 const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys",
-                                         "hae_keys", "ams_msgs", "rlc"};
+                                         "hae_keys", "ams_msgs", "key_msgs", "rlc"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -348,7 +350,7 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs", "bgls:rlc"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs", "bgls:key_msgs", "bgls:rlc"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on; on = false: part of the caller's stage
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -401,6 +403,27 @@ struct Engine {
     Scope sc(c, st, ST_DUP);
     HIPCHK(hipMemsetAsync(tab, 0, cap * 4, st));
     kl::dup_check(st, mv, n, (uint32_t*)tab, (uint32_t)(cap - 1), d_flags, bucket, n_buckets, dup_seed(), packed);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+
+  // The hash inputs of n (key, message) pairs whose message is derived from the key, built from keys that are on the device already
+  // (kl::key_msgs, k_keymsgs.hip): BGLS_KEYED_PREFIX -- key i's wire bytes || message i of mv (msg_bytes: the bytes of the n messages together;
+  // DistinctMsg*, bgls/blsDistinctMessage.go:51), BGLS_KEYED_POP -- the compressed key i alone (CheckAuthentication, bgls/blsKosk.go:66; mv
+  // unused, a key that does not compress sets FLAG_ENC).  *out: the view the call hashes in place of mv.
+  static int key_msgs(Ctx& c, hipStream_t st, int mode, const uint8_t* d_keys, MsgView mv, size_t msg_bytes, size_t n, uint32_t* d_flags, MsgView* out) {
+    if (n >= MAX_BATCH) return too_large();
+    const bool pop = mode == BGLS_KEYED_POP;
+    const size_t cap = pop ? n * (G2B / 2) : msg_bytes + n * G2B;
+    void *blob, *ooff = nullptr;
+    int rc;
+    if ((rc = c.get(WS_KEYED_BLOB, cap, &blob))) return rc;
+    if (!pop && mv.off && (rc = c.get(WS_KEYED_OFF, (n + 1) * 8, &ooff))) return rc;
+    if (pop) *out = {(const uint8_t*)blob, nullptr, G2B / 2, G2B / 2};
+    else if (mv.off) *out = {(const uint8_t*)blob, (const uint64_t*)ooff, 0, 0};
+    else *out = {(const uint8_t*)blob, nullptr, G2B + mv.len, G2B + mv.len};
+    Scope sc(c, st, ST_KEY_MSGS);
+    kl::key_msgs(st, C::CURVE_ID, mode, d_keys, n, mv, (uint8_t*)blob, cap, (uint64_t*)ooff, d_flags);
     HIPCHK(hipGetLastError());
     return 0;
   }

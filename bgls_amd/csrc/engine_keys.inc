@@ -267,8 +267,11 @@ int merged_flags_rc(uint32_t f) {
   return 0;
 }
 
+// distinct (bgls_verify_aggregate_distinct_h): message i is hashed behind key i's wire bytes, which every shard takes from its own d_wire
+// (Engine::key_msgs); there is no duplicate rule, so every shard, shard 0 included, uploads its own range of messages only.
 template <class C>
-int verify_aggregate_h_t(KeySet& ks, const uint8_t* sig, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups, uint8_t* gt_out) {
+int verify_aggregate_h_t(KeySet& ks, const uint8_t* sig, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups, uint8_t* gt_out,
+                         bool distinct = false) {
   typedef Engine<C> E;
   if (n != ks.n) return fail(BGLS_ERR_ARG, "message count differs from the key set's size");
   if (int bad = offsets_ok("msg_off", off, n, 0)) return bad;
@@ -285,22 +288,29 @@ int verify_aggregate_h_t(KeySet& ks, const uint8_t* sig, const uint8_t* blob, co
     const size_t cnt = sh.hi - sh.lo;
     // shard 0 holds ALL messages: the duplicate rule is a property of the whole list (two equal messages may sit in
     // different shards); the other shards upload their own range only
-    const size_t mlo = s == 0 ? 0 : sh.lo, mhi = s == 0 ? n : sh.hi;
+    const size_t mlo = s == 0 && !distinct ? 0 : sh.lo, mhi = s == 0 && !distinct ? n : sh.hi;
     const size_t bytes = off[mhi] - off[mlo];
     void *d_sig, *d_blob, *d_off, *d_flags;
     if ((r = c.get(WS_IN_A, E::G1B, &d_sig))) return r;
-    if ((r = c.get(WS_IN_C, bytes, &d_blob))) return r;
-    if ((r = c.get(WS_IN_D, (mhi - mlo + 1) * 8, &d_off))) return r;
     if ((r = c.get(WS_FLAGS, 16, &d_flags))) return r;
     HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
     if (s == 0) HIPCHK(hipMemcpyAsync(d_sig, sig, E::G1B, hipMemcpyHostToDevice, st));
-    if (bytes) HIPCHK(hipMemcpyAsync(d_blob, blob + off[mlo], bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_off, off + mlo, (mhi - mlo + 1) * 8, hipMemcpyHostToDevice, st));
-    // offsets keep their global values: the view's base is shifted instead (never dereferenced below d_blob)
-    MsgView all = {(const uint8_t*)d_blob - off[mlo], (const uint64_t*)d_off, 0, 0};
-    if (s == 0 && !allow_dups && (r = E::dup_scan(c, st, all, n, (uint32_t*)d_flags))) return r;
-    MsgView mine = all;
-    if (s == 0) mine.off = (const uint64_t*)d_off + sh.lo;      // sh.lo == 0; kept for clarity
+    MsgView mine;
+    if (distinct) {
+      Keyed keyed;
+      if ((r = upload_keyed_msgs(c, st, BGLS_KEYED_PREFIX, blob, off, mlo, mhi, &mine, &keyed))) return r;
+      if ((r = E::key_msgs(c, st, keyed.mode, (const uint8_t*)sh.d_wire, mine, keyed.msg_bytes, cnt, (uint32_t*)d_flags, &mine))) return r;
+    } else {
+      if ((r = c.get(WS_IN_C, bytes, &d_blob))) return r;
+      if ((r = c.get(WS_IN_D, (mhi - mlo + 1) * 8, &d_off))) return r;
+      if (bytes) HIPCHK(hipMemcpyAsync(d_blob, blob + off[mlo], bytes, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_off, off + mlo, (mhi - mlo + 1) * 8, hipMemcpyHostToDevice, st));
+      // offsets keep their global values: the view's base is shifted instead (never dereferenced below d_blob)
+      MsgView all = {(const uint8_t*)d_blob - off[mlo], (const uint64_t*)d_off, 0, 0};
+      if (s == 0 && !allow_dups && (r = E::dup_scan(c, st, all, n, (uint32_t*)d_flags))) return r;
+      mine = all;
+      if (s == 0) mine.off = (const uint64_t*)d_off + sh.lo;      // sh.lo == 0; kept for clarity
+    }
     if (ks.prepared) {
       if ((r = E::miller_product_prepared(c, st, s == 0 ? (const uint8_t*)d_sig : nullptr, (const uint32_t*)sh.d_prep, (const uint8_t*)sh.d_kinf, sh.n_pad, sh.ng,
                                           mine, cnt, (uint8_t*)sh.d_rec, (uint32_t*)d_flags)))

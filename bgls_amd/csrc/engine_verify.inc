@@ -31,6 +31,31 @@ int upload_msgs(Ctx& c, hipStream_t st, const uint8_t* blob, const uint64_t* off
   return 0;
 }
 
+// Messages lo .. hi of a host-pointer call whose hash inputs are built on the device (Engine::key_msgs), offsets already checked: the
+// blob range to WS_IN_C; messages of ONE length become the fixed-stride view and no offsets travel, else the hi - lo + 1 offsets go to
+// WS_IN_D with their caller's values and the view's base is shifted instead (never dereferenced below the blob).  *bytes: the bytes of
+// the messages together.  keyed.mode == BGLS_KEYED_POP: no messages, nothing is read or uploaded.
+struct Keyed { int mode; size_t msg_bytes; };
+int upload_keyed_msgs(Ctx& c, hipStream_t st, int mode, const uint8_t* blob, const uint64_t* off, size_t lo, size_t hi, MsgView* mv, Keyed* keyed) {
+  *keyed = {mode, 0};
+  *mv = {nullptr, nullptr, 0, 0};
+  if (mode == BGLS_KEYED_POP || hi == lo) return 0;
+  const size_t n = hi - lo, bytes = off[hi] - off[lo], len = off[lo + 1] - off[lo];
+  bool one_len = true;
+  for (size_t i = lo; i < hi && one_len; ++i) one_len = off[i + 1] - off[i] == len;
+  int rc;
+  void *d_blob, *d_off;
+  if ((rc = c.put(st, WS_IN_C, bytes ? blob + off[lo] : nullptr, bytes, &d_blob))) return rc;
+  keyed->msg_bytes = bytes;
+  if (one_len) {
+    *mv = {(const uint8_t*)d_blob, nullptr, len, len};
+    return 0;
+  }
+  if ((rc = c.put(st, WS_IN_D, off + lo, (n + 1) * 8, &d_off))) return rc;
+  *mv = {(const uint8_t*)d_blob - off[lo], (const uint64_t*)d_off, 0, 0};
+  return 0;
+}
+
 // The points of the sets of a host-pointer call on the device (PB bytes each): points off[0] .. off[n_sets] to *d_pts (WS_IN_B), the offsets
 // relative to off[0] to *d_off (WS_SEG_OFF) and to rel.  rel is the source of an asynchronous copy: the caller keeps it until it has
 // synchronised the stream.  Nothing of off is read when n_sets == 0.
@@ -56,8 +81,10 @@ int upload_key_sets(Ctx& c, hipStream_t st, size_t PB, const uint8_t* pts, const
     return fail(BGLS_ERR_ARG, "unknown curve id");               \
   } while (0)
 
+// distinct (DistinctMsgVerifyAggregateSignature, bgls/blsDistinctMessage.go:45-57): message i is hashed behind key i's wire bytes, put
+// there on the device, and there is no duplicate rule
 template <class C>
-int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups) {
+int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, int allow_dups, bool distinct = false) {
   typedef Engine<C> E;
   Call k;
   if (k.rc) return k.rc;
@@ -65,13 +92,18 @@ int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* b
   const hipStream_t st = k.st;
   int rc;
   MsgView mv;
+  Keyed keyed;
   void *d_sig, *d_keys, *d_flags, *d_part;
-  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  if (distinct) {
+    if ((rc = offsets_ok("msg_off", off, n, 0))) return rc;
+    if ((rc = upload_keyed_msgs(c, st, BGLS_KEYED_PREFIX, blob, off, 0, n, &mv, &keyed))) return rc;
+  } else if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
   if ((rc = c.put(st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
   if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
   if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
   if ((rc = c.get(WS_PART, E::GTB, &d_part))) return rc;
   HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
+  if (distinct && (rc = E::key_msgs(c, st, keyed.mode, (const uint8_t*)d_keys, mv, keyed.msg_bytes, n, (uint32_t*)d_flags, &mv))) return rc;
   if ((rc = E::miller_product(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n, !allow_dups, (uint8_t*)d_part,
                               (uint32_t*)d_flags)))
     return rc;
@@ -137,17 +169,21 @@ int batch_verdicts_run(Ctx& c, hipStream_t st, size_t n, const BatchOut& out, St
 
 // n_inst independent VerifyAggregateSignature calls (bgls/bgls.go:94-119) in one set of launches (Engine::miller_product_batch, which sets
 // d_iflags[b] for a duplicate message within instance b), then batch_verdicts_run's tail.
+// keyed != nullptr (the distinct-message batch): every message is hashed behind its key's wire bytes (Engine::key_msgs).
 template <class C>
 int verify_aggregate_batch_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
-                               int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+                               int allow_dups, uint8_t* verdicts, uint8_t* gt_out, const Keyed* keyed = nullptr) {
   return batch_verdicts_run<C>(c, st, n_inst, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t* d_iflags, uint32_t* d_flags) {
-    return Engine<C>::miller_product_batch(c, st, d_sigs, d_keys, mv, inst_off, n_inst, !allow_dups, d_part, d_iflags, d_flags);
+    MsgView hv = mv;
+    int r;
+    if (keyed && (r = Engine<C>::key_msgs(c, st, keyed->mode, d_keys, mv, keyed->msg_bytes, inst_off[n_inst], d_flags, &hv))) return r;
+    return Engine<C>::miller_product_batch(c, st, d_sigs, d_keys, hv, inst_off, n_inst, !allow_dups, d_part, d_iflags, d_flags);
   });
 }
 
 template <class C>
 int verify_aggregate_batch_t(const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst, const uint8_t* blob, const uint64_t* off,
-                             int allow_dups, uint8_t* verdicts, uint8_t* gt_out) {
+                             int allow_dups, uint8_t* verdicts, uint8_t* gt_out, bool distinct = false) {
   typedef Engine<C> E;
   Call k;
   if (k.rc) return k.rc;
@@ -156,20 +192,27 @@ int verify_aggregate_batch_t(const uint8_t* sigs, const uint8_t* keys, const uin
   int rc;
   const size_t n = inst_off[n_inst];
   MsgView mv;
+  Keyed keyed;
   void *d_sigs, *d_keys;
-  if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
+  if (distinct) {
+    if ((rc = offsets_ok("msg_off", off, n, 0))) return rc;
+    if ((rc = upload_keyed_msgs(c, st, BGLS_KEYED_PREFIX, blob, off, 0, n, &mv, &keyed))) return rc;
+  } else if ((rc = upload_msgs(c, st, blob, off, n, &mv))) return rc;
   if ((rc = c.put(st, WS_IN_A, sigs, n_inst * E::G1B, &d_sigs))) return rc;
   if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
-  return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
+  return verify_aggregate_batch_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out,
+                                       distinct ? &keyed : nullptr);
 }
 
 template <class C>
 int verify_aggregate_batch_dev_t(const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst, const void* d_msgs, size_t msg_len,
-                                 size_t msg_stride, int allow_dups, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+                                 size_t msg_stride, int allow_dups, uint8_t* verdicts, uint8_t* gt_out, void* stream, bool distinct = false) {
   Call k(stream);
   if (k.rc) return k.rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
-  return verify_aggregate_batch_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out);
+  const Keyed keyed = {BGLS_KEYED_PREFIX, (size_t)inst_off[n_inst] * msg_len};
+  return verify_aggregate_batch_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, inst_off, n_inst, allow_dups, verdicts, gt_out,
+                                       distinct ? &keyed : nullptr);
 }
 
 template <class C>
@@ -352,6 +395,73 @@ int verify_multi_sets_dev_t(const void* d_sigs, const void* d_keys, const void* 
   if ((rc = fetch_key_off(k.st, d_key_off, n_sets, max_set, false, d_keys, koff))) return rc;
   MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
   return verify_multi_sets_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, (const uint64_t*)d_key_off, n_sets, max_set, mv, verdicts, gt_out);
+}
+
+// n single-signature checks whose message is derived from the key (DistinctMsgVerifySingleSignature, bgls/blsDistinctMessage.go:37-40;
+// CheckAuthentication, bgls/blsKosk.go:59-69): item b is the signature d_sigs[b], the key d_keys[b] and, under BGLS_KEYED_PREFIX, message b
+// of mv.  The hash inputs are built on the device (Engine::key_msgs), then Engine::miller_multi_sets with the keys themselves as the
+// per-set key sums and batch_verdicts_run's tail.
+template <class C>
+int verify_single_keyed_run(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const Keyed& keyed, size_t n, uint8_t* verdicts,
+                            uint8_t* gt_out) {
+  return batch_verdicts_run<C>(c, st, n, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t*, uint32_t* d_flags) {
+    MsgView hv;
+    int r = Engine<C>::key_msgs(c, st, keyed.mode, d_keys, mv, keyed.msg_bytes, n, d_flags, &hv);
+    return r ? r : Engine<C>::miller_multi_sets(c, st, d_sigs, d_keys, hv, n, d_part, d_flags);
+  });
+}
+
+template <class C>
+int verify_single_keyed_t(int mode, const uint8_t* sigs, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, uint8_t* verdicts,
+                          uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  MsgView mv;
+  Keyed keyed;
+  void *d_sigs, *d_keys;
+  if ((rc = upload_keyed_msgs(c, st, mode, blob, off, 0, n, &mv, &keyed))) return rc;
+  if ((rc = c.put(st, WS_IN_A, sigs, n * E::G1B, &d_sigs))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
+  return verify_single_keyed_run<C>(c, st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, keyed, n, verdicts, gt_out);
+}
+
+template <class C>
+int verify_single_distinct_dev_t(const void* d_sigs, const void* d_keys, size_t n, const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts,
+                                 uint8_t* gt_out, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  const MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_single_keyed_run<C>(k.c, k.st, (const uint8_t*)d_sigs, (const uint8_t*)d_keys, mv, {BGLS_KEYED_PREFIX, n * msg_len}, n, verdicts, gt_out);
+}
+
+// HashToG1 of the n inputs Engine::key_msgs builds from host keys (and messages): the hash of DistinctMsgSign / Authenticate.
+template <class C>
+int hash_to_g1_keyed_t(int mode, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, uint8_t* out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  if (n == 0) return 0;
+  MsgView mv;
+  Keyed keyed;
+  void *d_keys, *d_g1s, *d_out, *d_flags;
+  if ((rc = upload_keyed_msgs(c, st, mode, blob, off, 0, n, &mv, &keyed))) return rc;
+  if ((rc = c.put(st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
+  if ((rc = c.get(WS_G1S, n * sizeof(Aff<F1<C>>), &d_g1s))) return rc;
+  if ((rc = c.get(WS_IN_A, n * E::G1B, &d_out))) return rc;
+  if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
+  HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
+  if ((rc = E::key_msgs(c, st, mode, (const uint8_t*)d_keys, mv, keyed.msg_bytes, n, (uint32_t*)d_flags, &mv))) return rc;
+  if ((rc = E::hash_to_g1(c, st, mv, n, (Aff<F1<C>>*)d_g1s, (uint32_t*)d_flags))) return rc;
+  kl::g1_to_bytes<C>(st, (const Aff<F1<C>>*)d_g1s, n, (uint8_t*)d_out);
+  HIPCHK(hipGetLastError());
+  return read_flags(c, st, d_flags, true, out, d_out, n * E::G1B);
 }
 
 // ---- the combined check: many multi-signatures under one random linear combination per group (bgls_verify_multi_sets_combined) ----

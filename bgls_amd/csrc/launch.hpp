@@ -123,6 +123,13 @@ void hae_wsum_main(hipStream_t st, const uint8_t* keys, const uint64_t* key_off,
 void ams_msgs(hipStream_t st, const uint8_t* apks, const uint32_t* signers, const uint64_t* signer_off, size_t n, size_t total, MsgView mv, unsigned g2b,
               const uint64_t* hoff, uint8_t* blob, uint32_t* inst_flags);
 
+// ---- k_keymsgs.hip: hash inputs made of the keys themselves, n of them (curve: BGLS_CURVE_*; keys: n G2 wire rows).  mode BGLS_KEYED_PREFIX:
+// input i = key row i || message i of mv at out_off(i) = (start of message i - start of message 0) + i G2B of blob, nothing written past
+// cap bytes; out_off (device, n + 1 words) is written when mv is in the offset form and may be NULL when it is the fixed-stride one (the
+// blob then has the stride G2B + mv.len).  mode BGLS_KEYED_POP: input i = the compressed key i at stride G2B / 2, mv / cap / out_off
+// unused, a key that does not compress sets FLAG_ENC in flags.
+void key_msgs(hipStream_t st, int curve, int mode, const uint8_t* keys, size_t n, MsgView mv, uint8_t* blob, size_t cap, uint64_t* out_off, uint32_t* flags);
+
 // ---- k_millerams.hip: the Miller loop of n accountable-subgroup multisignature checks, one accumulator per item, ams_per_block items per
 // block.  Item b: (g1a[b], q2a[b]) and (g1b[b], q2b[b]) walked (keys as wire bytes) and, on alt-bn128, (sigs[b], g2) on the generator lines
 // -- GT bytes (no final exponentiation) to out_bytes + b GTB; on BLS12-381 the two walked pairs alone, six w-basis Fp2 to out_w + 6 b (the

@@ -225,6 +225,29 @@ class CurveSystem:
         raw = bytes(o)
         return [Point(self, G1, raw[i * s:(i + 1) * s]) for i in range(n)]
 
+    def HashToG1Keyed(self, keys, msgs=None):
+        """HashToG1 of inputs derived from G2 keys, built on the device (bgls_hash_to_g1_keyed): key i's uncompressed bytes followed by
+        msgs[i] (the hash of DistinctMsgSign), or with msgs None the compressed key alone (the hash of Authenticate)."""
+        n = len(keys)
+        if msgs is not None and len(msgs) != n:
+            raise ValueError("keys and msgs differ in length")
+        if any(not (isinstance(k, Point) and k.curve is self and k.group == G2) for k in keys):
+            raise ValueError("HashToG1Keyed takes G2 Points of this curve")
+        blob, off = None, None
+        if msgs is not None:
+            ms = [bytes(m) for m in msgs]
+            blob = _lib.buf(b"".join(ms))
+            off = (ctypes.c_uint64 * (n + 1))()
+            for i, m in enumerate(ms):
+                off[i + 1] = off[i] + len(m)
+        s = self._pt_size(G1)
+        o = _lib.out(n * s)
+        rc = _lib.load().bgls_hash_to_g1_keyed(self.id, 0 if msgs is not None else 1, _lib.buf(b"".join(k.raw for k in keys)), blob, off, n, o)
+        if rc != 0:
+            raise RuntimeError("bgls_hash_to_g1_keyed: %d %s" % (rc, _lib.last_error()))
+        raw = bytes(o)
+        return [Point(self, G1, raw[i * s:(i + 1) * s]) for i in range(n)]
+
     def Pair(self, p1, p2):
         return self.PairingProduct([p1], [p2])
 

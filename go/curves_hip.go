@@ -385,6 +385,190 @@ func (ks *HipKeySet) VerifyMulti(aggsig Point, msg []byte) bool {
 	return ok
 }
 
+// VerifyAggregateDistinct is bgls.DistinctMsgVerifyAggregateSignature (bgls/blsDistinctMessage.go:45-57) against the resident keys:
+// every GPU of the set puts its keys' wire bytes in front of the messages itself, nothing is prefixed here.
+func (ks *HipKeySet) VerifyAggregateDistinct(aggsig Point, msgs [][]byte) bool {
+	s, ok := aggsig.(*hipPoint)
+	if !ok || s.c != ks.c || s.group != C.BGLS_G1 || len(msgs) != ks.n {
+		return false
+	}
+	blob, off := hipMsgBlob(msgs)
+	ok = C.bgls_verify_aggregate_distinct_h(ks.h, p(s.raw), p(blob), &off[0], C.size_t(ks.n), nil) == 1
+	runtime.KeepAlive(ks)
+	return ok
+}
+
+// hipMsgBlob lays messages out as one blob with len(msgs)+1 offsets.
+func hipMsgBlob(msgs [][]byte) ([]byte, []C.uint64_t) {
+	off := make([]C.uint64_t, len(msgs)+1)
+	var blob []byte
+	for i, m := range msgs {
+		off[i] = C.uint64_t(len(blob))
+		blob = append(blob, m...)
+	}
+	off[len(msgs)] = C.uint64_t(len(blob))
+	return blob, off
+}
+
+// ---- distinct messages (bgls/blsDistinctMessage.go) and key registration (bgls/blsKosk.go:44-69) ----------------------------
+// The message that is hashed is derived from the signer's key; the engine derives it on the device from the keys it has there.
+
+// HipHashToG1Keyed is HashToG1 of key i's uncompressed bytes followed by msgs[i] (the hash of DistinctMsgSign), or with msgs == nil of
+// the compressed key alone (the hash of Authenticate).  nil on failure.
+func HipHashToG1Keyed(curve CurveSystem, keys []Point, msgs [][]byte) []Point {
+	c, ok := curve.(*hipCurve)
+	if !ok || (msgs != nil && len(msgs) != len(keys)) {
+		return nil
+	}
+	kb, ok2 := hipKeyBytes(c, keys)
+	if !ok2 {
+		return nil
+	}
+	if len(keys) == 0 {
+		return []Point{}
+	}
+	mode := C.int(C.BGLS_KEYED_POP)
+	var blob []byte
+	var op *C.uint64_t
+	if msgs != nil {
+		mode = C.BGLS_KEYED_PREFIX
+		var off []C.uint64_t
+		blob, off = hipMsgBlob(msgs)
+		op = &off[0]
+	}
+	sz := c.size(C.BGLS_G1)
+	out := make([]byte, len(keys)*sz)
+	if C.bgls_hash_to_g1_keyed(c.id, mode, p(kb), p(blob), op, C.size_t(len(keys)), p(out)) != 0 {
+		return nil
+	}
+	pts := make([]Point, len(keys))
+	for i := range pts {
+		pts[i] = &hipPoint{c, C.BGLS_G1, out[i*sz : (i+1)*sz]}
+	}
+	return pts
+}
+
+// HipVerifyAggregateDistinct is bgls.DistinctMsgVerifyAggregateSignature (bgls/blsDistinctMessage.go:45-57) in one call.
+func HipVerifyAggregateDistinct(curve CurveSystem, aggsig Point, keys []Point, msgs [][]byte) bool {
+	c, ok := curve.(*hipCurve)
+	s, ok2 := aggsig.(*hipPoint)
+	if !ok || !ok2 || s.group != C.BGLS_G1 || len(keys) != len(msgs) {
+		return false
+	}
+	kb, ok3 := hipKeyBytes(c, keys)
+	if !ok3 {
+		return false
+	}
+	blob, off := hipMsgBlob(msgs)
+	return C.bgls_verify_aggregate_distinct(c.id, p(s.raw), p(kb), p(blob), &off[0], C.size_t(len(keys))) == 1
+}
+
+// HipVerifyAggregateDistinctBatch is len(aggsigs) independent DistinctMsgVerifyAggregateSignature calls in one batch, one bool per
+// instance, with HipVerifyAggregateBatch's conventions: an instance that is not made of this curve's points (or whose lengths differ)
+// is false, a call that fails as a whole is settled instance by instance.
+func HipVerifyAggregateDistinctBatch(curve CurveSystem, aggsigs []Point, pubkeys [][]Point, msgs [][][]byte) []bool {
+	out := make([]bool, len(aggsigs))
+	c, ok := curve.(*hipCurve)
+	if !ok || len(pubkeys) != len(aggsigs) || len(msgs) != len(aggsigs) {
+		return out
+	}
+	var batch []int
+	var sb, kb []byte
+	var flat [][]byte
+	ioff := []C.uint64_t{0}
+	for b := range aggsigs {
+		s, ok := aggsigs[b].(*hipPoint)
+		if !ok || s.c != c || s.group != C.BGLS_G1 || len(pubkeys[b]) != len(msgs[b]) {
+			continue
+		}
+		one, ok2 := hipKeyBytes(c, pubkeys[b])
+		if !ok2 {
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		kb = append(kb, one...)
+		flat = append(flat, msgs[b]...)
+		ioff = append(ioff, ioff[len(ioff)-1]+C.uint64_t(len(pubkeys[b])))
+	}
+	if len(batch) == 0 {
+		return out
+	}
+	blob, moff := hipMsgBlob(flat)
+	verdicts := make([]byte, len(batch))
+	rc := C.bgls_verify_aggregate_distinct_batch(c.id, p(sb), p(kb), &ioff[0], C.size_t(len(batch)), p(blob), &moff[0], p(verdicts), nil)
+	for i, b := range batch {
+		if rc >= 0 {
+			out[b] = verdicts[i] == 1
+		} else {
+			out[b] = HipVerifyAggregateDistinct(curve, aggsigs[b], pubkeys[b], msgs[b])
+		}
+	}
+	return out
+}
+
+// hipVerifySingleKeyed runs the items made of this curve's points through one bgls_verify_single_distinct_batch (msgs != nil) or
+// bgls_check_authentication_batch call; any other item is false, and a call that fails as a whole is settled through batches of one.
+func hipVerifySingleKeyed(curve CurveSystem, sigs []Point, pubkeys []Point, msgs [][]byte) []bool {
+	out := make([]bool, len(sigs))
+	c, ok := curve.(*hipCurve)
+	if !ok || len(pubkeys) != len(sigs) || (msgs != nil && len(msgs) != len(sigs)) {
+		return out
+	}
+	var batch []int
+	var sb, kb []byte
+	var ms [][]byte
+	for b := range sigs {
+		s, ok := sigs[b].(*hipPoint)
+		k, ok2 := pubkeys[b].(*hipPoint)
+		if !ok || !ok2 || s.c != c || k.c != c || s.group != C.BGLS_G1 || k.group != C.BGLS_G2 {
+			continue
+		}
+		batch = append(batch, b)
+		sb = append(sb, s.raw...)
+		kb = append(kb, k.raw...)
+		if msgs != nil {
+			ms = append(ms, msgs[b])
+		}
+	}
+	if len(batch) == 0 {
+		return out
+	}
+	verdicts := make([]byte, len(batch))
+	var rc C.int
+	if msgs != nil {
+		blob, moff := hipMsgBlob(ms)
+		rc = C.bgls_verify_single_distinct_batch(c.id, p(sb), p(kb), p(blob), &moff[0], C.size_t(len(batch)), p(verdicts), nil)
+	} else {
+		rc = C.bgls_check_authentication_batch(c.id, p(kb), p(sb), C.size_t(len(batch)), p(verdicts), nil)
+	}
+	for i, b := range batch {
+		if rc >= 0 {
+			out[b] = verdicts[i] == 1
+		} else if len(batch) > 1 {
+			var one [][]byte
+			if msgs != nil {
+				one = [][]byte{msgs[b]}
+			}
+			out[b] = hipVerifySingleKeyed(curve, []Point{sigs[b]}, []Point{pubkeys[b]}, one)[0]
+		}
+	}
+	return out
+}
+
+// HipVerifySingleDistinctBatch is len(sigs) independent DistinctMsgVerifySingleSignature calls (bgls/blsDistinctMessage.go:37-40).
+func HipVerifySingleDistinctBatch(curve CurveSystem, sigs []Point, pubkeys []Point, msgs [][]byte) []bool {
+	if msgs == nil {
+		msgs = [][]byte{}
+	}
+	return hipVerifySingleKeyed(curve, sigs, pubkeys, msgs)
+}
+
+// HipCheckAuthenticationBatch is len(pubkeys) independent CheckAuthentication calls (bgls/blsKosk.go:59-69).
+func HipCheckAuthenticationBatch(curve CurveSystem, pubkeys []Point, authentications []Point) []bool {
+	return hipVerifySingleKeyed(curve, authentications, pubkeys, nil)
+}
+
 func hipKeyBytes(c *hipCurve, keys []Point) ([]byte, bool) {
 	kb := make([]byte, 0, len(keys)*c.size(C.BGLS_G2))
 	for _, k := range keys {

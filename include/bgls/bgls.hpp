@@ -108,6 +108,18 @@ class KeySet {
     if (!ok_ || aggsig.curve != curve_ || aggsig.group != BGLS_G1) return false;
     return bgls_verify_multi_h(h_, aggsig.raw.data(), msg.data(), msg.size()) == 1;
   }
+  // DistinctMsgVerifyAggregateSignature (bgls/blsDistinctMessage.go:45-57) against the resident keys, whose wire bytes go in front of the
+  // messages on the device
+  bool DistinctMsgVerifyAggregateSignature(const Point& aggsig, const std::vector<Bytes>& msgs) const {
+    if (!ok_ || msgs.size() != n_ || aggsig.curve != curve_ || aggsig.group != BGLS_G1) return false;
+    Bytes blob;
+    std::vector<uint64_t> off(msgs.size() + 1, 0);
+    for (size_t i = 0; i < msgs.size(); ++i) {
+      blob.insert(blob.end(), msgs[i].begin(), msgs[i].end());
+      off[i + 1] = blob.size();
+    }
+    return bgls_verify_aggregate_distinct_h(h_, aggsig.raw.data(), blob.data(), off.data(), n_, nullptr) == 1;
+  }
 
  private:
   const CurveSystem* curve_;
@@ -379,6 +391,110 @@ inline std::vector<bool> KoskVerifySingleSignatures(const CurveSystem* curve, co
   std::vector<std::vector<Point>> keys;
   for (const Point& k : pubKeys) keys.push_back({k});
   return KoskVerifyMultiSignatures(curve, sigs, keys, msgs);
+}
+// ---- distinct messages (bgls/blsDistinctMessage.go) and key registration (bgls/blsKosk.go:44-69): the message that is hashed is derived
+// from the signer's key, and the library derives it on the device -- nothing is prefixed here ----
+// DistinctMsgSign, bgls/blsDistinctMessage.go:23-34
+inline Point DistinctMsgSign(const CurveSystem* curve, const Bytes& sk_be32, const Bytes& msg) {
+  std::vector<Bytes> one(1, msg);
+  std::vector<Point> h = curve->HashToG1Keyed({LoadPublicKey(curve, sk_be32)}, &one);
+  return h.empty() ? Point{} : h[0].Mul(sk_be32);
+}
+// Authenticate, bgls/blsKosk.go:44-55: a signature on the marshalled key
+inline Point Authenticate(const CurveSystem* curve, const Bytes& sk_be32) {
+  std::vector<Point> h = curve->HashToG1Keyed({LoadPublicKey(curve, sk_be32)});
+  return h.empty() ? Point{} : h[0].Mul(sk_be32);
+}
+// DistinctMsgVerifyAggregateSignature, bgls/blsDistinctMessage.go:45-57
+inline bool DistinctMsgVerifyAggregateSignature(const CurveSystem* curve, const Point& aggsig, const std::vector<Point>& keys, const std::vector<Bytes>& msgs) {
+  if (keys.size() != msgs.size() || aggsig.curve != curve || aggsig.group != BGLS_G1) return false;
+  Bytes kb, blob;
+  if (!detail::g2_bytes(curve, keys, kb)) return false;
+  std::vector<uint64_t> off(msgs.size() + 1, 0);
+  for (size_t i = 0; i < msgs.size(); ++i) {
+    blob.insert(blob.end(), msgs[i].begin(), msgs[i].end());
+    off[i + 1] = blob.size();
+  }
+  return bgls_verify_aggregate_distinct(curve->id, aggsig.raw.data(), kb.data(), blob.data(), off.data(), keys.size()) == 1;
+}
+// B independent DistinctMsgVerifyAggregateSignature calls in ONE bgls_verify_aggregate_distinct_batch call, with verifyAggSigs' conventions
+inline std::vector<bool> DistinctMsgVerifyAggregateSignatures(const CurveSystem* curve, const std::vector<Point>& aggsigs,
+                                                              const std::vector<std::vector<Point>>& keys, const std::vector<std::vector<Bytes>>& msgs) {
+  std::vector<bool> out(aggsigs.size(), false);
+  if (keys.size() != aggsigs.size() || msgs.size() != aggsigs.size()) return out;
+  std::vector<size_t> batch;
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> ioff(1, 0), moff(1, 0);
+  for (size_t b = 0; b < aggsigs.size(); ++b) {
+    Bytes one;
+    if (aggsigs[b].curve != curve || aggsigs[b].group != BGLS_G1 || keys[b].size() != msgs[b].size() || !detail::g2_bytes(curve, keys[b], one)) continue;
+    batch.push_back(b);
+    sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+    kb.insert(kb.end(), one.begin(), one.end());
+    ioff.push_back(ioff.back() + keys[b].size());
+    for (const Bytes& m : msgs[b]) {
+      blob.insert(blob.end(), m.begin(), m.end());
+      moff.push_back(blob.size());
+    }
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = bgls_verify_aggregate_distinct_batch(curve->id, sb.data(), kb.data(), ioff.data(), batch.size(), blob.data(), moff.data(), verdicts.data(),
+                                                      nullptr);
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const size_t b = batch[i];
+    out[b] = rc >= 0 ? verdicts[i] == 1 : DistinctMsgVerifyAggregateSignature(curve, aggsigs[b], keys[b], msgs[b]);
+  }
+  return out;
+}
+namespace detail {
+// the items made of this curve's points through ONE bgls_verify_single_distinct_batch (msgs given) or bgls_check_authentication_batch
+// call; any other item is false, and a call that fails as a whole is settled item by item through batches of one
+inline std::vector<bool> verify_single_keyed(const CurveSystem* curve, const std::vector<Point>& sigs, const std::vector<Point>& pubKeys,
+                                             const std::vector<Bytes>* msgs) {
+  const size_t n = sigs.size();
+  std::vector<bool> out(n, false);
+  if (pubKeys.size() != n || (msgs && msgs->size() != n)) return out;
+  std::vector<size_t> batch;
+  Bytes sb, kb, blob;
+  std::vector<uint64_t> moff(1, 0);
+  for (size_t b = 0; b < n; ++b) {
+    if (sigs[b].curve != curve || sigs[b].group != BGLS_G1 || pubKeys[b].curve != curve || pubKeys[b].group != BGLS_G2) continue;
+    batch.push_back(b);
+    sb.insert(sb.end(), sigs[b].raw.begin(), sigs[b].raw.end());
+    kb.insert(kb.end(), pubKeys[b].raw.begin(), pubKeys[b].raw.end());
+    if (msgs) blob.insert(blob.end(), (*msgs)[b].begin(), (*msgs)[b].end());
+    moff.push_back(blob.size());
+  }
+  if (batch.empty()) return out;
+  std::vector<uint8_t> verdicts(batch.size(), 0);
+  const int rc = msgs ? bgls_verify_single_distinct_batch(curve->id, sb.data(), kb.data(), blob.data(), moff.data(), batch.size(), verdicts.data(), nullptr)
+                      : bgls_check_authentication_batch(curve->id, kb.data(), sb.data(), batch.size(), verdicts.data(), nullptr);
+  if (rc < 0 && batch.size() > 1) {
+    for (size_t b : batch) {
+      const std::vector<Bytes> one(1, msgs ? (*msgs)[b] : Bytes());
+      out[b] = verify_single_keyed(curve, {sigs[b]}, {pubKeys[b]}, msgs ? &one : nullptr)[0];
+    }
+    return out;
+  }
+  for (size_t i = 0; i < batch.size(); ++i) out[batch[i]] = rc >= 0 && verdicts[i] == 1;
+  return out;
+}
+}  // namespace detail
+// B independent DistinctMsgVerifySingleSignature calls (bgls/blsDistinctMessage.go:37-40) in one batch
+inline std::vector<bool> DistinctMsgVerifySingleSignatures(const CurveSystem* curve, const std::vector<Point>& sigs, const std::vector<Point>& pubKeys,
+                                                           const std::vector<Bytes>& msgs) {
+  return detail::verify_single_keyed(curve, sigs, pubKeys, &msgs);
+}
+inline bool DistinctMsgVerifySingleSignature(const CurveSystem* curve, const Point& sig, const Point& pubKey, const Bytes& msg) {
+  return DistinctMsgVerifySingleSignatures(curve, {sig}, {pubKey}, {msg})[0];
+}
+// B independent CheckAuthentication calls (bgls/blsKosk.go:59-69) in one batch
+inline std::vector<bool> CheckAuthentications(const CurveSystem* curve, const std::vector<Point>& pubKeys, const std::vector<Point>& authentications) {
+  return detail::verify_single_keyed(curve, authentications, pubKeys, nullptr);
+}
+inline bool CheckAuthentication(const CurveSystem* curve, const Point& pubKey, const Point& authentication) {
+  return CheckAuthentications(curve, {pubKey}, {authentication})[0];
 }
 // KoskVerifyBatchMultiSignature, bgls/blsKosk.go:126-133: one call -- every key set summed in one launch, ONE aggregate verification
 inline bool KoskVerifyBatchMultiSignature(const CurveSystem* curve, const std::vector<Point>& aggsigs, const std::vector<std::vector<Point>>& pubkeys,

@@ -92,6 +92,23 @@ struct CurveSystem {
     if (bgls_hash_to_g1(id, message.data(), off, 1, o.data()) != 0) return Point{};
     return Point{this, BGLS_G1, o};
   }
+  // HashToG1 of inputs derived from G2 keys, built on the device (bgls_hash_to_g1_keyed): key i's uncompressed bytes followed by
+  // (*msgs)[i] (the hash of DistinctMsgSign), or with msgs == nullptr the compressed key alone (the hash of Authenticate); empty on failure
+  std::vector<Point> HashToG1Keyed(const std::vector<Point>& keys, const std::vector<Bytes>* msgs = nullptr) const {
+    std::vector<Point> out;
+    if (msgs && msgs->size() != keys.size()) return out;
+    Bytes kb, blob, o(keys.size() * size(BGLS_G1));
+    std::vector<uint64_t> off(keys.size() + 1, 0);
+    for (size_t i = 0; i < keys.size(); ++i) {
+      if (keys[i].curve != this || keys[i].group != BGLS_G2) return out;
+      kb.insert(kb.end(), keys[i].raw.begin(), keys[i].raw.end());
+      if (msgs) blob.insert(blob.end(), (*msgs)[i].begin(), (*msgs)[i].end());
+      off[i + 1] = blob.size();
+    }
+    if (bgls_hash_to_g1_keyed(id, msgs ? BGLS_KEYED_PREFIX : BGLS_KEYED_POP, kb.data(), blob.data(), off.data(), keys.size(), o.data()) != 0) return out;
+    for (size_t i = 0; i < keys.size(); ++i) out.push_back(Point{this, BGLS_G1, Bytes(o.begin() + i * size(BGLS_G1), o.begin() + (i + 1) * size(BGLS_G1))});
+    return out;
+  }
   std::pair<PointT, bool> Pair(const Point& a, const Point& b) const { return PairingProduct({a}, {b}); }
   // one C call for the whole slice (replaces concurrentPairingProduct, curves/curve.go:125-170)
   std::pair<PointT, bool> PairingProduct(const std::vector<Point>& p1, const std::vector<Point>& p2) const {

@@ -99,6 +99,38 @@ int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* k
                                 const uint8_t* msg_blob, const uint64_t* msg_off, int allow_duplicates, uint8_t* verdicts,
                                 uint8_t* gt_out);
 
+/* ---- distinct messages (bgls/blsDistinctMessage.go) and key registration (bgls/blsKosk.go:44-69) ----------------------------------
+ * The message that is hashed is derived from the signer's key: key i's uncompressed wire bytes followed by message i
+ * (BGLS_KEYED_PREFIX: append(keys[i].MarshalUncompressed(), msgs[i]...), blsDistinctMessage.go:51; the key bytes go in verbatim, as the
+ * caller or the key set holds them), or the compressed key alone (BGLS_KEYED_POP: pubkey.Marshal(), blsKosk.go:66).  The library builds
+ * these hash inputs on the device from the keys it has there; callers pass plain messages and never prefix anything.  There is no
+ * duplicate rule (blsDistinctMessage.go:53-56), everything else is the sibling call's contract.
+ *
+ * HashToG1 of the n built inputs (n G1 points to g1_out, as bgls_hash_to_g1 returns them for a host-built blob): the hash of
+ * DistinctMsgSign (mode BGLS_KEYED_PREFIX) and of Authenticate (mode BGLS_KEYED_POP: msg_blob / msg_off are ignored and may be NULL; a
+ * key that does not compress is BGLS_ERR_ENCODING, as in bgls_compress_points).  Any other mode is BGLS_ERR_ARG. */
+#define BGLS_KEYED_PREFIX 0
+#define BGLS_KEYED_POP 1
+int bgls_hash_to_g1_keyed(int curve, int mode, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n,
+                          uint8_t* g1_out);
+/* DistinctMsgVerifyAggregateSignature (blsDistinctMessage.go:45-57): returns 1 / 0 / < 0 exactly as
+ * bgls_verify_aggregate(..., allow_duplicates = 1) does on messages the caller prefixed itself. */
+int bgls_verify_aggregate_distinct(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob,
+                                   const uint64_t* msg_off, size_t n);
+/* n_inst independent DistinctMsgVerifyAggregateSignature calls: bgls_verify_aggregate_batch's contract (limits, whole-call errors,
+ * return value, gt_out) with allow_duplicates = 1 on the prefixed messages. */
+int bgls_verify_aggregate_distinct_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint64_t* inst_off, size_t n_inst,
+                                         const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* gt_out);
+/* n independent DistinctMsgVerifySingleSignature calls (blsDistinctMessage.go:37-40): item b is sigs[b], keys[b] and message b.
+ * bgls_verify_multi_sets' contract on one-key sets with the prefixed messages (verdicts, gt_out, whole-call errors, return value; n == 0
+ * returns 0). */
+int bgls_verify_single_distinct_batch(int curve, const uint8_t* sigs, const uint8_t* keys, const uint8_t* msg_blob,
+                                      const uint64_t* msg_off, size_t n, uint8_t* verdicts, uint8_t* gt_out);
+/* n independent CheckAuthentication calls (blsKosk.go:59-69): item b is the key keys[b] and its proof of possession auths[b] (G1), a
+ * signature on the compressed key.  The single-signature batch above with BGLS_KEYED_POP inputs. */
+int bgls_check_authentication_batch(int curve, const uint8_t* keys, const uint8_t* auths, size_t n, uint8_t* verdicts,
+                                    uint8_t* gt_out);
+
 /* verifyMultiSignature (bgls/bgls.go:89-92): apk = sum(keys) (AggregatePoints,
  * curves/curve.go:73-121) then VerifySingleSignature (bgls/bgls.go:59-70) on msg.
  * KoskVerifyMultiSignature (bgls/blsKosk.go:117-120) is this call with 0x01 prepended to msg. */
@@ -452,6 +484,13 @@ int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, 
 int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst,
                                     const void* d_msgs, size_t msg_len, size_t msg_stride, int allow_duplicates,
                                     uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_verify_aggregate_distinct_batch / bgls_verify_single_distinct_batch with signatures, keys and fixed-stride messages on the device,
+ * parameters as in bgls_verify_aggregate_batch_dev / bgls_verify_multi_sets_dev (item b of the single form: d_sigs[b], d_keys[b]). */
+int bgls_verify_aggregate_distinct_batch_dev(int curve, const void* d_sigs, const void* d_keys, const uint64_t* inst_off, size_t n_inst,
+                                             const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts,
+                                             uint8_t* gt_out, void* stream);
+int bgls_verify_single_distinct_batch_dev(int curve, const void* d_sigs, const void* d_keys, size_t n, const void* d_msgs,
+                                          size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* gt_out, void* stream);
 /* verify_multi with keys already on the device. */
 int bgls_verify_multi_dev(int curve, const void* d_sig, const void* d_keys, size_t n, const void* d_msg,
                           size_t msg_len, void* stream);
@@ -492,6 +531,11 @@ int bgls_verify_aggregate_h(bgls_keys_t handle, const uint8_t* sig, const uint8_
  * bgls/bgls.go:113-114; the identity iff the verdict is 1): canonical bytes, identical for any number of devices. */
 int bgls_verify_aggregate_h_gt(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n,
                                int allow_duplicates, uint8_t* gt_out);
+/* DistinctMsgVerifyAggregateSignature against a resident key set (any number of shards, prepared or not): every shard builds its
+ * hash inputs from its own resident wire bytes and uploads only its own range of messages.  n must equal the set's size
+ * (BGLS_ERR_ARG).  gt_out: NULL or one GT element, byte-equal to bgls_verify_aggregate_h_gt on messages the caller prefixed. */
+int bgls_verify_aggregate_distinct_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg_blob, const uint64_t* msg_off,
+                                     size_t n, uint8_t* gt_out);
 /* verifyMultiSignature (bgls/bgls.go:89-92) against a ONE-device key set, signature and message already on the device, on the
  * calling thread's context and the given stream: the key sum reads the set's resident sum-ready records -- the keys are the
  * reference's already-constructed Points (parsed and validated at upload), so nothing but the n - 1 additions of
