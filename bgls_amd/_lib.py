@@ -114,6 +114,8 @@ SIGNATURES = {
     "bgls_profile_get": (ci, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong)]),
     "bgls_probe_mad_peak": (ci, [ctypes.POINTER(ctypes.c_double)]),
     "bgls_selftest_exception_barrier": (ci, [ci]),
+    "bgls_selftest_fill_workspaces": (ci, [ci, ctypes.c_uint64, u64p]),
+    "bgls_selftest_workspace_caps": (ci, [ctypes.POINTER(sz), ci]),
 }
 
 _lib = None

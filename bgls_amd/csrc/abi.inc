@@ -616,6 +616,73 @@ int bgls_selftest_exception_barrier(int kind) try {
   }
 } BGLS_ABI_GUARD
 
+// Self-test of the workspace contract (DESIGN.md section 5, "Workspace contract"; tests/test_gpu_stale_workspace.py): every cached
+// workspace of every ready context of every device, over its whole CAPACITY (a slot keeps bytes + bytes / 4 and is never cleared on
+// reuse), and the context's pinned result words are set to `byte`; with a key-set handle also the exchange records d_rec / d_all of each
+// of its shards.  Nothing else is touched: not the device tables, not the resident key data, not a caller's buffer.
+// All or nothing: every ready context is asked first, and while any has a verification in flight the call refuses (BGLS_ERR_ARG) before
+// one byte is set -- the words are that verification's.  *bytes_filled (nullable) is the bytes set, in every outcome: a verification
+// submitted by another thread between the question and a context's turn ends the call there, with what was set until then.
+// The fills are enqueued on each context's OWN stream and waited for: work a caller has queued on a stream of its own (the *_dev entries)
+// is not ordered against them -- the caller of this hook synchronises such a stream first.
+int bgls_selftest_fill_workspaces(int byte, uint64_t keys, uint64_t* bytes_filled) try {
+  if (bytes_filled) *bytes_filled = 0;
+  int cnt = 0;
+  const hipError_t e0 = hipGetDeviceCount(&cnt);
+  if (e0 != hipSuccess || cnt <= 0) return fail(BGLS_ERR_NO_DEVICE, "no HIP device available", e0);
+  std::shared_ptr<KeySet> ks;
+  if (keys && !(ks = keyset(keys))) return fail(BGLS_ERR_ARG, "unknown key set handle");
+  int dev0 = 0;
+  HIPCHK(hipGetDevice(&dev0));
+  struct Restore { int d; ~Restore() { (void)hipSetDevice(d); } } restore{dev0};
+  uint64_t total = 0;
+  struct Report { uint64_t* out; const uint64_t& v; ~Report() { if (out) *out = v; } } report{bytes_filled, total};
+  Ctx* all = ctx_pool();
+  for (int k = 0; k < MAX_DEVICES * NCTX; ++k) {          // the question first: no context is touched while one refuses
+    std::lock_guard<std::mutex> lk(all[k].mu);
+    if (all[k].ready && all[k].res_pending) return in_flight();
+  }
+  for (int k = 0; k < MAX_DEVICES * NCTX; ++k) {
+    Ctx& c = all[k];
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (!c.ready) continue;
+    if (c.res_pending) return in_flight();
+    HIPCHK(hipSetDevice(c.device));
+    for (auto& w : c.ws)
+      if (w.first && w.second) {
+        HIPCHK(hipMemsetAsync(w.first, byte, w.second, c.stream));
+        total += w.second;
+      }
+    HIPCHK(hipStreamSynchronize(c.stream));
+    memset(c.h_res, byte, 64);
+    total += 64;
+  }
+  if (ks) {
+    std::lock_guard<std::mutex> lk_set(ks->mu);
+    const size_t REC = (ks->curve == 0 ? Engine<BN254>::GTB : Engine<BLS381>::GTB) + REC_PAD;
+    for (auto& sh : ks->shards) {
+      HIPCHK(hipSetDevice(sh.device));
+      if (sh.d_rec) { HIPCHK(hipMemset(sh.d_rec, byte, REC)); total += REC; }
+      if (sh.d_all) { HIPCHK(hipMemset(sh.d_all, byte, REC * ks->shards.size())); total += REC * ks->shards.size(); }
+      HIPCHK(hipDeviceSynchronize());
+    }
+  }
+  return 0;
+} BGLS_ABI_GUARD
+
+// The capacities of the calling thread's context's workspace slots (0: never allocated) to caps[0 .. min(n, slots)); returns the slot
+// count.  Without a device: the no-device code, as every entry that would enter the context.
+int bgls_selftest_workspace_caps(size_t* caps, int n) try {
+  if (n < 0 || (n > 0 && !caps)) return fail(BGLS_ERR_ARG, "NULL argument");
+  int cnt = 0;
+  const hipError_t e0 = hipGetDeviceCount(&cnt);
+  if (e0 != hipSuccess || cnt <= 0) return fail(BGLS_ERR_NO_DEVICE, "no HIP device available", e0);
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  for (int i = 0; i < n && i < WS_NUM; ++i) caps[i] = c.ready ? c.ws[i].second : 0;
+  return WS_NUM;
+} BGLS_ABI_GUARD
+
 int bgls_probe_mad_peak(double* mac_per_s) try {
   if (!mac_per_s) return fail(BGLS_ERR_ARG, "NULL argument");
   Call k;

@@ -576,6 +576,15 @@ int bgls_probe_mad_peak(double* mac_per_s);
  * 6 bad_alloc on a shard's host thread) and returns the error code the barrier maps it to (BGLS_ERR_NOMEM / _HIP / _ARG).
  * No entry point lets an exception unwind into the caller (the reference never panics: curves/curve.go:15-22). */
 int bgls_selftest_exception_barrier(int kind);
+/* Self-tests of the workspace contract: the library never frees or clears its device scratch between calls, so
+ * every word a kernel reads must have been written earlier in the same call.  bgls_selftest_fill_workspaces sets the whole capacity of
+ * every cached workspace of every ready context of every device, and the contexts' pinned result words, to `byte`; with keys != 0 also
+ * the exchange records of that key set's shards.  Device tables, resident key data and caller buffers are left alone.  It waits for the
+ * fills, refuses with BGLS_ERR_ARG before it sets one byte while a verification is in flight on any context, and reports the bytes set
+ * in *bytes_filled (nullable).  The fills run on the contexts' own streams: synchronise a stream of your own first.  bgls_selftest_workspace_caps writes the capacity of each workspace slot of the calling thread's context (0: never
+ * allocated) to caps[0 .. min(n, slots)) and returns the slot count.  Test-only: no binding mirrors them. */
+int bgls_selftest_fill_workspaces(int byte, uint64_t keys, uint64_t* bytes_filled);
+int bgls_selftest_workspace_caps(size_t* caps, int n);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,26 @@ def test_no_silent_cpu_fallback():
     assert lib.bgls_verify_multi(0, o, o, 0, o, 0) == -4
 
 
+def test_workspace_selftests_are_exported_and_need_a_device():
+    """The two test-only exports of the workspace contract exist in the shipped library, and without a device
+    they fail with the no-device code like every other entry: nothing is filled, nothing is reported as filled."""
+    import torch
+    from bgls_amd import _lib
+    lib = _lib.load()
+    for name in ("bgls_selftest_fill_workspaces", "bgls_selftest_workspace_caps"):
+        assert name in _lib.SIGNATURES and hasattr(lib, name) and name in declared_functions()
+    assert lib.bgls_selftest_workspace_caps(None, 4) == -1            # argument check comes first, with or without a device
+    if torch.cuda.is_available():
+        return
+    filled = ctypes.c_uint64(77)
+    assert lib.bgls_selftest_fill_workspaces(0xFF, 0, ctypes.byref(filled)) == -4 and "device" in _lib.last_error().lower()
+    assert filled.value == 0
+    assert lib.bgls_selftest_fill_workspaces(0, 0, None) == -4
+    caps = (ctypes.c_size_t * 64)()
+    assert lib.bgls_selftest_workspace_caps(caps, 64) == -4 and "device" in _lib.last_error().lower()
+    assert not any(caps)
+
+
 def test_product_never_imports_oracle():
     """The product path must not route through the checker."""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "bgls_amd")):
