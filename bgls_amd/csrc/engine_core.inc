@@ -305,16 +305,6 @@ bool g1x() { return !legacy(LG_G1); }
 // G2 key sums: true = one partial per LANE PAIR on the carry-free limbs (k_sumpair.hip, rx_jacpair.hpp), false = k_sum_main
 bool sum_pairs() { return !legacy(LG_SUM); }
 
-#ifdef BGLS_DEV
-// development builds only: BGLS_MILLER_DBG=1/2 times the producer / consumer half of the fused Miller kernels (WRONG results)
-int miller_dbg() {
-  static const int v = [] { const char* e = getenv("BGLS_MILLER_DBG"); return e ? atoi(e) : 0; }();
-  return v;
-}
-#else
-constexpr int miller_dbg() { return 0; }
-#endif
-
 // ST_SUM is opened ONCE per key sum (main pass + tree + conversion); ST_SUM_MAIN brackets the main-pass kernel alone, inside it
 // ST_SCATTER and ST_EPI are opened by the batch of independent verifications only (Engine::miller_product_batch): the padded layout
 // of its pairs and its batched epilogue; ST_BB_KEYS by the batched Boneh-Boyen verification only (Engine::miller_bb: its Q_b = m_b g2 + U_b + r_b V_b)
@@ -998,7 +988,7 @@ struct Engine {
         const size_t p0 = blk0 * 64;
         const size_t np = npairs - p0 < nblocks * 64 ? npairs - p0 : nblocks * 64;
         const long long sig_at = (blk0 == 0 && sig && !cofactor) ? (long long)(sig - (g1s + p0)) : -1LL;
-        kl::miller_ab64<C>(st, (unsigned)nblocks, g1s + p0, g2s + p0 * G2B, np, sig_at, gl, (Fp2<C>*)pa + blk0 * 10 * 6, d_flags, miller_dbg(), (uint32_t*)qp);
+        kl::miller_ab64<C>(st, (unsigned)nblocks, g1s + p0, g2s + p0 * G2B, np, sig_at, gl, (Fp2<C>*)pa + blk0 * 10 * 6, d_flags, (uint32_t*)qp);
       }
       HIPCHK(hipGetLastError());
     }

@@ -9,17 +9,12 @@ namespace kl {
 #ifdef BGLS_LEGACY_KERNELS           // k_miller_ab64, the 32-bit fused Miller kernel behind BGLS_MILLER_SHAPE=5: `make LEGACY=1` only
 template <class C>
 void miller_ab64(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, long long sig_at,
-                 const LineCoeffs<C>* gen_lines, Fp2<C>* out, uint32_t* flags, int dbg, uint32_t* qp) {
+                 const LineCoeffs<C>* gen_lines, Fp2<C>* out, uint32_t* flags, uint32_t* qp) {
   const size_t lds = Coop64<C>::BLOCK_BYTES;
-#ifdef BGLS_DEV
-  if (dbg == 1) { k_miller_ab64<C, 1><<<nblocks, 128, lds, st>>>(g1s, g2s, n, sig_at, gen_lines, out, flags, 0u, qp); return; }
-  if (dbg == 2) { k_miller_ab64<C, 2><<<nblocks, 128, lds, st>>>(g1s, g2s, n, sig_at, gen_lines, out, flags, 0u, qp); return; }
-#endif
-  (void)dbg;
   k_miller_ab64<C><<<nblocks, 128, lds, st>>>(g1s, g2s, n, sig_at, gen_lines, out, flags, 0u, qp);
 }
 template void miller_ab64<BGLS_MILLER_CURVE>(hipStream_t, unsigned, const Aff<F1<BGLS_MILLER_CURVE>>*, const uint8_t*, size_t, long long,
-                                             const LineCoeffs<BGLS_MILLER_CURVE>*, Fp2<BGLS_MILLER_CURVE>*, uint32_t*, int, uint32_t*);
+                                             const LineCoeffs<BGLS_MILLER_CURVE>*, Fp2<BGLS_MILLER_CURVE>*, uint32_t*, uint32_t*);
 #endif
 
 // ---- prepared key sets (prepared.hpp): the fold on the carry-free limbs of the Miller kernel (nine of 29 bits / fourteen of 28)

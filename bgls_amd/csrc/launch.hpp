@@ -70,10 +70,10 @@ template <class C> void fb_build(hipStream_t st, int group, void* table);
 template <class C> void fb_scale(hipStream_t st, int group, const void* table, const uint8_t* scalars, size_t n, uint8_t* out);
 template <class C> void scale_g1_inplace(hipStream_t st, Aff<F1<C>>* pts, const uint8_t* w16, size_t n);
 
-// ---- k_miller_bn.hip / k_miller_bls.hip   (dbg != 0 only in -DBGLS_DEV builds: timing variants, wrong results)
+// ---- k_miller_bn.hip / k_miller_bls.hip   (the legacy library only)
 template <class C>
 void miller_ab64(hipStream_t st, unsigned nblocks, const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, long long sig_at,
-                 const LineCoeffs<C>* gen_lines, Fp2<C>* out, uint32_t* flags, int dbg, uint32_t* qp);
+                 const LineCoeffs<C>* gen_lines, Fp2<C>* out, uint32_t* flags, uint32_t* qp);
 template <class C> constexpr size_t miller_qp_bytes(size_t nblocks) { return nblocks * 64 * 6 * C::L * 4; }    // parked Q, P of every producer lane
 
 // ---- k_millerx_{bn,bls}.hip (NP = 60), k_millerx64_{bn,bls}.hip (NP = 64)

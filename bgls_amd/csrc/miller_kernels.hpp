@@ -3,8 +3,6 @@
 //   k_miller_ab64   fused producer/consumer block, 64 pairings, 32-bit limbs (both curves; the shape used when one
 //                   verification has the machine to itself)
 //   k_miller_s60    fused producer/consumer block, 60 pairings, 28-bit-limb consumer (alt-bn128, throughput mode)
-// DBG template values other than 0 are timing variants with WRONG results; they are only instantiated in
-// development builds (-DBGLS_DEV) and never reachable from the shipped library.
 #pragma once
 #include "dev_common.hpp"
 #include "coop.hpp"
@@ -84,10 +82,8 @@ struct Coop64 {
 // multiplies its two lines into one 5-coefficient element (coop_write_line_pair).  Lanes 60..63 feed the
 // single-line slot of groups 0..3, the (-sigma, g2) line goes to the single slot of group 4, groups 5..9 keep
 // the constant 1 there.  The consumer folds 3 five-term elements + 1 three-term line per step.
-// DBG (development only, BGLS_AB64_DBG): 1 = producer work only, 2 = consumer work only -- wrong results, used to
-// time the two halves of the pipeline separately.
 // R28 (alt-bn128): the consumer works on 28-bit limbs (coop_r28.hpp); the producer converts what it stores.
-template <class C, int DBG = 0, bool R28 = false>
+template <class C, bool R28 = false>
 __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, long long sig_at,
                                                         const LineCoeffs<C>* gen_lines, Fp2<C>* out, uint32_t* flags, unsigned swap_mask, u32* qp) {
   typedef Coop64<C, R28> K;
@@ -141,7 +137,6 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
     QP<C>::park(myqp, Q, P);
     int buf = 0, step = 0;
     auto publish = [&](LineCapture<C>& cap) __attribute__((always_inline)) {
-      if constexpr (DBG == 2) { ++step; __syncthreads(); buf ^= 1; return; }
       if (!valid) { cap.e[0] = f2_one<C>(); cap.e[1] = f2_zero<C>(); cap.e[2] = f2_zero<C>(); }
       const LReg r = {tgb + (buf ? K::RL2 : K::RL), K::NENT};
       if (paired) {
@@ -160,7 +155,7 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
       }
       ++step;
       wave_sync();
-      if constexpr (DBG != 3) __syncthreads();
+      __syncthreads();
       buf ^= 1;
     };
 #pragma unroll 1
@@ -169,7 +164,7 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
         const u32* q = QP<C>::launder(myqp);
         const Fp<C> px = QP<C>::ld_fp(q, QP<C>::PX), py = QP<C>::ld_fp(q, QP<C>::PY);
         LineCapture<C> cap{{}, px, py};
-        if constexpr (DBG != 2) dbl_step_emit<C>(T, cap);
+        dbl_step_emit<C>(T, cap);
         publish(cap);
       }
       const int d = C::LOOP_NAF[i];
@@ -178,7 +173,7 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
         const Fp<C> px = QP<C>::ld_fp(q, QP<C>::PX), py = QP<C>::ld_fp(q, QP<C>::PY);
         const Fp2<C> qx = QP<C>::ld_f2(q, QP<C>::QX), qy = QP<C>::ld_f2(q, QP<C>::QY);
         LineCapture<C> cap{{}, px, py};
-        if constexpr (DBG != 2) add_step_emit<C>(T, qx, d > 0 ? qy : f2_neg<C>(qy), cap);
+        add_step_emit<C>(T, qx, d > 0 ? qy : f2_neg<C>(qy), cap);
         publish(cap);
       }
     }
@@ -189,7 +184,7 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
         Fp2<C> x1 = f2_mul<C>(f2_conj<C>(QP<C>::ld_f2(q, QP<C>::QX)), gamma_const<C>(1, 2));
         Fp2<C> y1 = f2_mul<C>(f2_conj<C>(QP<C>::ld_f2(q, QP<C>::QY)), gamma_const<C>(1, 3));
         LineCapture<C> cap{{}, px, py};
-        if constexpr (DBG != 2) add_step_emit<C>(T, x1, y1, cap);
+        add_step_emit<C>(T, x1, y1, cap);
         publish(cap);
       }
       {
@@ -198,11 +193,11 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
         Fp2<C> x2 = f2_mul<C>(QP<C>::ld_f2(q, QP<C>::QX), gamma_const<C>(2, 2));
         Fp2<C> y2 = f2_neg<C>(f2_mul<C>(QP<C>::ld_f2(q, QP<C>::QY), gamma_const<C>(2, 3)));
         LineCapture<C> cap{{}, px, py};
-        if constexpr (DBG != 2) add_step_emit<C>(T, x2, y2, cap);
+        add_step_emit<C>(T, x2, y2, cap);
         publish(cap);
       }
     }
-    if (DBG == 0 && valid && f2_is_zero<C>(T.Z)) atomicOr(flags, FLAG_DEGENERATE);     // a degenerate point step leaves Z = 0 (miller_x.hpp)
+    if (valid && f2_is_zero<C>(T.Z)) atomicOr(flags, FLAG_DEGENERATE);     // a degenerate point step leaves Z = 0 (miller_x.hpp)
   } else {
     // ---------------- consumer: 10 groups x 6 lanes; per step 3 line pairs + 1 single line
     const bool live = lane < 60;
@@ -222,7 +217,6 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
       coop_publish28<C>(rbo, j, fj, live);
       int buf = 0;
       auto fold = [&]() {
-        if constexpr (DBG == 1) { buf ^= 1; return; }
         const int rlo = gb + (buf ? K::RL2 : K::RL);
 #pragma unroll 1
         for (int m = 0; m < 3; ++m) {
@@ -235,20 +229,18 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
       };
 #pragma unroll 1
       for (int i = 1; i < C::LOOP_LEN; ++i) {
-        if constexpr (DBG != 3) __syncthreads();
-        if constexpr (DBG != 1) {
-          fj = coop_sqr_sym28<C>(rbo, j);
-          coop_publish28<C>(rbo, j, fj, live);
-        }
+        __syncthreads();
+        fj = coop_sqr_sym28<C>(rbo, j);
+        coop_publish28<C>(rbo, j, fj, live);
         fold();
         if (C::LOOP_NAF[i] != 0) {
-          if constexpr (DBG != 3) __syncthreads();
+          __syncthreads();
           fold();
         }
       }
-      if constexpr (DBG != 3) __syncthreads();
+      __syncthreads();
       fold();
-      if constexpr (DBG != 3) __syncthreads();
+      __syncthreads();
       fold();
       if (live) out[((size_t)blockIdx.x * 10 + g) * 6 + j] = from_r28<C>(fj);
       return;
@@ -258,7 +250,6 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
     coop_publish<C, K::XF>(gb + K::RB, j, fj, live);
     int buf = 0;
     auto fold = [&]() {
-      if constexpr (DBG == 1) { buf ^= 1; return; }
       const LReg rl = {gb + (buf ? K::RL2 : K::RL), K::NENT};
 #pragma unroll 1
       for (int m = 0; m < 3; ++m) {
@@ -271,21 +262,19 @@ __global__ void __launch_bounds__(128, 2) k_miller_ab64(const Aff<F1<C>>* g1s, c
     };
 #pragma unroll 1
     for (int i = 1; i < C::LOOP_LEN; ++i) {
-      if constexpr (DBG != 3) __syncthreads();
-      if constexpr (DBG != 1) {
-        fj = coop_sqr_sym_inl<C, K::XF>(rb, j);
-        coop_publish<C, K::XF>(gb + K::RB, j, fj, live);
-      }
+      __syncthreads();
+      fj = coop_sqr_sym_inl<C, K::XF>(rb, j);
+      coop_publish<C, K::XF>(gb + K::RB, j, fj, live);
       fold();
       if (C::LOOP_NAF[i] != 0) {
-        if constexpr (DBG != 3) __syncthreads();
+        __syncthreads();
         fold();
       }
     }
     if constexpr (C::CURVE_ID == 0) {
-      if constexpr (DBG != 3) __syncthreads();
+      __syncthreads();
       fold();
-      if constexpr (DBG != 3) __syncthreads();
+      __syncthreads();
       fold();
     } else {
       if (j & 1) fj = f2_neg<C>(fj);                      // x < 0: f^(p^6), w -> -w

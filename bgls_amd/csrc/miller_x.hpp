@@ -15,14 +15,15 @@
 // Why the hand-over stays two block barriers on ONE buffer (round 6, profiles/r6/miller_handover.md).  The stamps show who waits:
 // the consumer arrives last at A in 70 % of the steps and waits there 9.5 % of its time -- all of it in the first twenty steps of
 // a block's life, when its two producers are the YOUNGEST waves of their SIMDs (the issue arbiter serves the oldest ready wave
-// first: a block's period falls from 112 k clocks to 62 k as it ages).  -DMX_EXP_FLAGS=D replaces the barriers by LDS sequence
-// words and lets the producers store D / 2 steps ahead (wrong results beyond D = 2: the single buffer is overwritten -- timing
-// only): D = 2 / 3 / 4 / 6 measured 53.3 / 53.2 / 52.9 / 52.6 ms (alt-bn128), 84.2 / 84.6 / 84.6 / 84.2 ms (BLS12-381) -- a ring of
+// first: a block's period falls from 112 k clocks to 62 k as it ages).  A hand-over through LDS sequence words instead of the
+// barriers, with the producers storing D / 2 steps ahead (a timing experiment: beyond D = 2 the single buffer is overwritten),
+// measured 53.3 / 53.2 / 52.9 / 52.6 ms for D = 2 / 3 / 4 / 6 (alt-bn128), 84.2 / 84.6 / 84.6 / 84.2 ms (BLS12-381) -- a ring of
 // three half-step slots, the most that 160 KB of LDS hold at four blocks per CU, would buy 0.3 %, two whole buffers 0.9 %.
-// Likewise the consumer's exposed LDS round trips: fetching every operand one stage ahead (-DMX_EXP_Q, rx.hpp ux_dot_k2q) takes a
-// consumer wave ALONE from 38.9 to 34.9 ms and the whole kernel from 53.9 to 55.2 ms: the old blocks' consumers issue denser and
-// the young blocks' producers starve longer.  What bounds the kernel is instruction issue: 2.73e10 vector instructions per launch
-// at the 4.4-4.5 clocks a mixed stream of three waves per SIMD pays per instruction (probe in tools/mb_stamps.hip) are 50 of the 54 ms.
+// Likewise the consumer's exposed LDS round trips: fetching every operand one stage ahead takes a consumer wave ALONE from 38.9 to
+// 34.9 ms and the whole kernel from 53.9 to 55.2 ms: the old blocks' consumers issue denser and the young blocks' producers starve
+// longer.  (Both experiments: profiles/r6/miller_handover.md and LAB_NOTES.md; their code left with the round-6 switches.)
+// What bounds the kernel is instruction issue: 2.73e10 vector instructions per launch at the 4.4-4.5 clocks a mixed stream of
+// three waves per SIMD pays per instruction (probe in tools/mb_stamps.hip) are 50 of the 54 ms.
 //
 // What the 32-bit kernels (k_miller_ab64 / k_miller_s60) lose and this one does not: three VALU instructions per multiplier
 // instruction (carry add, re-zeroed addend) -- here every dot product is bare v_mad_u64_u32 into 64-bit columns; a producer
@@ -33,7 +34,7 @@
 // other kernels: the partial products are bit-identical to k_miller_ab64's.
 //
 //
-// XL, "xi on the line" (alt-bn128's 60-pairing block on the 29-bit form, MX<BN254W, 60>; -DMX_NO_XL for the A/B).  A fold's wrapped terms need a
+// XL, "xi on the line" (alt-bn128's 60-pairing block on the 29-bit form, MX<BN254W, 60>).  A fold's wrapped terms need a
 // factor xi = w^6:  c_j = sum_t L_t B_((j - sh t) mod 6) xi^[j < sh t],  sh = {0, 1, 3}.  Every other form keeps xi copies of the ACCUMULATOR: the
 // consumer -- the wave that arrives last at barrier A -- runs ux_mulxi in each of its seven publishes of a doubling step, on all six lanes, to
 // have xi e_5 (t = 1) and xi e_3..e_5 (t = 2) ready.  XL puts the factor on the LINE, xi (L_t B_k) = (xi L_t) B_k: the producer lane pair that
@@ -79,25 +80,15 @@ namespace bgls {
 // pairings, the batch a lone VerifyAggregateSignature of BASELINE configs 2 / 3 submits.
 // The number form a curve's kernel runs on: alt-bn128 on nine limbs of 29 bits (BN254W, round 5: 81 instead of 100 multiplier
 // instructions per limb product), BLS12-381 on fourteen of 28 (thirteen of 30 leave no head-room in a 64-bit column at all).
-// -DMX_BN_W28 keeps alt-bn128 on ten limbs of 28 bits (A/B measurements).
 template <class C>
 struct MxForm { typedef C type; };
-#ifndef MX_BN_W28
 template <>
 struct MxForm<BN254> { typedef BN254W type; };
-#endif
 
 // XL ("xi on the line", alt-bn128's 60-form on the 29-bit number form only): the xi of a fold's wrapped terms is applied to the LINE by the producers,
 // once per line, instead of to the accumulator by every publish of the consumer -- xi (L_t B_k) = (xi L_t) B_k.  See the kernel's header comment and
-// the XL layout below.  -DMX_NO_XL keeps the kernel on the accumulator's xi copies (A/B measurements).
-template <class C, int NP>
-struct MxXlDefault { static constexpr bool value = false; };
-#ifndef MX_NO_XL
-template <>
-struct MxXlDefault<BN254W, 60> { static constexpr bool value = true; };
-#endif
-
-template <class C, int NP = 60, bool XL_ = MxXlDefault<C, NP>::value>
+// the XL layout below.
+template <class C, int NP = 60, bool XL_ = (std::is_same<C, BN254W>::value && NP == 60)>
 struct MX {
   static_assert(NP == 60 || NP == 64, "pairings per block");
   static constexpr bool XL = XL_;
@@ -139,17 +130,10 @@ struct MX {
   // the hash points' coordinates (-yP, xP per pairing, read by both lanes of its pair at every step) live in LDS where a
   // quarter of a CU's 160 KB has room for them next to the groups, else in the lanes' global workspace (BLS12-381, NP = 64)
   static constexpr int PQ = 10 * GROUP_DW;            // [NP pairings][2] halves
-#ifndef MX_P_LDS_LIMIT
-#define MX_P_LDS_LIMIT 40960
-#endif
-  static constexpr bool P_IN_LDS = (10 * GROUP_DW + NP * 2 * HS) * 4 <= MX_P_LDS_LIMIT;
-  static constexpr int SEQ_DW = 10 * GROUP_DW + (P_IN_LDS ? NP * 2 * HS : 0);          // MX_EXP_FLAGS: four sequence words behind everything else
-#ifdef MX_EXP_FLAGS
-  static constexpr int BLOCK_BYTES = (SEQ_DW + 16) * 4;
-#else
+  static constexpr int P_LDS_LIMIT = 40960;
+  static constexpr bool P_IN_LDS = (10 * GROUP_DW + NP * 2 * HS) * 4 <= P_LDS_LIMIT;
   static constexpr int BLOCK_BYTES = (10 * GROUP_DW + (P_IN_LDS ? NP * 2 * HS : 0)) * 4;
   static_assert(!XL || (BLOCK_BYTES <= 40960 && !P_IN_LDS), "XL: four blocks per CU; the hash points' coordinates are parked in the workspace");
-#endif
   static constexpr int NPARK_Q = C::CURVE_ID == 0 ? 6 : 2;                  // xq yq [x1 y1 x2 y2]
   static constexpr int NPARK = NPARK_Q + (P_IN_LDS ? 0 : 2);                // ... nyP xP   (PS dwords each)
   static constexpr int PS = (NL + 3) & ~3;                                  // parked values stay 16-byte aligned
@@ -269,18 +253,6 @@ __device__ __forceinline__ Ux2<C> mx_fold(int gb, int m, int j, bool glo = false
   // powers of w the line's three entries sit at: {0, 1, 3} (D-type twist) / {0, 2, 3} (M-type), as arithmetic on t: a table in
   // constant memory costs a scalar load and a wait for it in front of every operand fetch
   auto sh = [](int t) { return C::TWIST_D ? t + (t == 2 ? 1 : 0) : t + (t >= 1 ? 1 : 0); };
-#ifdef MX_EXP_Q
-  if constexpr (C::RX_NL <= 10)
-    return ux_dot_k2q<C, 3>(
-      [&](int t, int h) { return mx_ld_half<C, K::PACKED>(gb + K::line_off(3 * m + t) + h * K::HS, h != 0); },
-      [&](int t, int h) {
-        int k = j - sh(t);
-        const int wrap = k < 0 ? 1 : 0;
-        k += 6 * wrap;
-        return mx_ld_half<C, K::PACKED>(gb + K::acc_off(k, wrap) + h * K::HS, h != 0);
-      });
-  else
-#endif
   return ux_dot_k2p<C, 3, (C::RX_NL <= 10)>(
       [&](int t, int h) { return mx_ld_half<C, K::PACKED>(gb + K::line_off(3 * m + t) + h * K::HS, h != 0); },
       [&](int t, int h) {
@@ -419,36 +391,22 @@ struct MxPark {
 
 // rot_mode: how the three roles are dealt to the three waves of a block (the hardware places wave w of a block on some
 // SIMD; rotating the roles from block to block keeps each SIMD's mix of producers and consumers even)
-// DBG (development tools only, never instantiated in the library): 1 = producer work only, 2 = consumer work only -- wrong
-// results, used to time the two roles separately.
 // (Round 3's variant with two consumer waves per block -- 20 partial products, the squaring done twice -- measured slower in
 // steady state and is gone.)
-// DBG == 4 (development tools only, tools/mb_stamps.hip): time stamps (s_memtime, low word) at the arrival at and the release from the two
-// barriers of every line step, per wave of the sampled blocks: who waits for whom.  Record of a wave: MX_STAMP_DW dwords,
-// [0] HW_ID [1] XCC_ID [2..3] s_memrealtime at the start [4..5] at the end [6] role [7] s_memtime at the start [8] at the end [9] line steps,
-// [16 + 4 s + k]: step s, k = 0 arrival at A, 1 release from A, 2 arrival at B, 3 release from B.
-// MX_EXP_FLAGS = D (experiment): the hand-over through LDS sequence words instead of the two block barriers.  cons (word 0) counts the HALF steps the
-// consumer has finished with (three lines each), prod[w] (words 1, 2) the steps producer wave w has stored.  A producer may store step s once
-// cons >= 2 s + 2 - D: D = 2 is the single line buffer (what the barriers enforce), D = 3 a ring of three half-step slots, D = 4 two whole buffers.
-// With D > 2 on the single-buffer layout the lines are overwritten early: WRONG RESULTS, timing only -- it prices the decoupling before the ring is built.
-__device__ __forceinline__ u32 mx_seq_ld(int dw) {
-  u32 v;
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(dw * 4) : "memory");
-  return (u32)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ void mx_seq_st(int dw, u32 val) {
-  asm volatile("ds_write_b32 %0, %1" : : "v"(dw * 4), "v"(val) : "memory");
-}
-__device__ __forceinline__ void mx_seq_wait(int dw, int target) {
-  while ((int)mx_seq_ld(dw) - target < 0) __builtin_amdgcn_s_sleep(1);
-}
-
+// DBG: the library instantiates MX_DBG_NONE only; the others are the two instruments of the development tools.
+//   MX_DBG_PRODUCERS / MX_DBG_CONSUMER (tools/mb_x60.hip, tools/mb_stamps.hip): only that role does its work -- wrong results, used to time
+//   the two roles separately.
+//   MX_DBG_STAMPS (tools/mb_stamps.hip): time stamps (s_memtime, low word) at the arrival at and the release from the two barriers of every
+//   line step, per wave of the sampled blocks: who waits for whom.  Record of a wave: MX_STAMP_DW dwords,
+//   [0] HW_ID [1] XCC_ID [2..3] s_memrealtime at the start [4..5] at the end [6] role [7] s_memtime at the start [8] at the end [9] line steps,
+//   [16 + 4 s + k]: step s, k = 0 arrival at A, 1 release from A, 2 arrival at B, 3 release from B.
+constexpr int MX_DBG_NONE = 0, MX_DBG_PRODUCERS = 1, MX_DBG_CONSUMER = 2, MX_DBG_STAMPS = 4;
 constexpr int MX_STAMP_STEPS = 96;
 constexpr int MX_STAMP_DW = 16 + 4 * MX_STAMP_STEPS;
 constexpr int MX_STAMP_EVERY = 16;          // every sixteenth block is sampled
 template <int DBG>
 __device__ __forceinline__ void mx_stamp(u32* rec, int slot) {
-  if constexpr (DBG == 4) {
+  if constexpr (DBG == MX_DBG_STAMPS) {
     if (rec != nullptr) {
       const unsigned long long t = __builtin_readcyclecounter();
       if ((threadIdx.x & 63) == 0) rec[slot] = (u32)t;
@@ -458,12 +416,10 @@ __device__ __forceinline__ void mx_stamp(u32* rec, int slot) {
   }
 }
 
-#ifndef MX_WAVES
-#define MX_WAVES 3          // waves per SIMD the register allocation is made for (tools: -DMX_WAVES=4 tries five blocks per CU)
-#endif
-template <class C, int DBG = 0, int NP = 60>
-__global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, Fp2<C>* out, uint32_t* flags, u32* park,
-                                                       int rot_mode, u32* rec_dbg) {
+template <class C, int DBG = MX_DBG_NONE, int NP = 60>
+__global__ void __launch_bounds__(192, 3) k_miller_x60(const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, Fp2<C>* out, uint32_t* flags, u32* park,
+                                                int rot_mode, u32* rec_dbg) {
+  static_assert(DBG == MX_DBG_NONE || DBG == MX_DBG_PRODUCERS || DBG == MX_DBG_CONSUMER || DBG == MX_DBG_STAMPS, "instrument");
   typedef MX<C, NP> K;
   constexpr int NL = C::RX_NL;
   constexpr int PPW = NP / 2;                                    // pairings (lane pairs at work) per producer wave: 30 / 32
@@ -478,15 +434,6 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
   extern __shared__ u32 lds_roles[];
   const int rmode = rot_mode & 3;
   int role;
-  if constexpr (DBG == 3) {          // development tools only (tools/mb_lone.hip): where and when every wave runs; rec_dbg is the record buffer (nullptr in the library)
-    if (lane == 0) {
-      u32* rec = rec_dbg + ((size_t)blockIdx.x * 3 + w) * 8;
-      const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-      rec[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      rec[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-      rec[2] = (u32)t; rec[3] = (u32)(t >> 32);
-    }
-  }
   if (rmode == 0) {
     const u32 hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);                             // HW_REG_HW_ID
     const int simd = (int)((hw >> 4) & 3u);                                               // bits 5:4
@@ -505,13 +452,9 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     role = w + rot;
     if (role >= 3) role -= 3;
   }
-#ifdef MX_EXP_FLAGS
-  if (threadIdx.x < 4) lds_roles[K::SEQ_DW + threadIdx.x] = 0u;
-  __syncthreads();
-#endif
-  u32* srec = nullptr;                 // DBG == 4: this wave's stamp record (sampled blocks only)
+  u32* srec = nullptr;                 // MX_DBG_STAMPS: this wave's stamp record (sampled blocks only; rec_dbg is nullptr in the library)
   int sstep = 0;
-  if constexpr (DBG == 4) {
+  if constexpr (DBG == MX_DBG_STAMPS) {
     if (rec_dbg != nullptr && blockIdx.x % MX_STAMP_EVERY == 0) {
       srec = rec_dbg + ((size_t)(blockIdx.x / MX_STAMP_EVERY) * 3 + w) * MX_STAMP_DW;
       if (lane == 0) {
@@ -601,13 +544,12 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
         if (entry != 0) e[entry + 2] = pair_mulxi_half<C>(e[entry], odd);
       }
     };
-    int pstep = 0;                        // MX_EXP_FLAGS: line steps stored so far
     auto hand_over = [&]() __attribute__((always_inline)) {
       // the constant line 1 for a pairing that is not there (a batch's ragged end, a key or hash point at infinity).  Decided per WAVE first: the lanes
       // that own no pairing never store their line, so only an OWNED invalid pairing needs the selects, and a wave without one -- all but the last
       // block of a batch -- branches over the 3 NL of them
-      if (DBG == 2 || __builtin_amdgcn_ballot_w64(owner && !valid) != 0) {
-        if (DBG == 2 || !valid) {
+      if (DBG == MX_DBG_CONSUMER || __builtin_amdgcn_ballot_w64(owner && !valid) != 0) {
+        if (DBG == MX_DBG_CONSUMER || !valid) {
           e[0] = odd ? ux_zero<C>() : ux_load<C>(C::RX_ONE);
           e[1] = ux_zero<C>();
           e[2] = ux_zero<C>();
@@ -615,11 +557,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
         }
       }
       mx_stamp<DBG>(srec, 16 + 4 * sstep);
-#ifdef MX_EXP_FLAGS
-      mx_seq_wait(K::SEQ_DW, 2 * pstep + 2 - (MX_EXP_FLAGS));
-#else
       __syncthreads();                    // A: the consumer has finished with the previous lines
-#endif
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
       if (owner) {
         if constexpr (K::XL) {
@@ -634,14 +572,9 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
         }
       }
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
-#ifdef MX_EXP_FLAGS
-      ++pstep;
-      mx_seq_st(K::SEQ_DW + 1 + role, (u32)pstep);          // LDS serves a wave's accesses in order: the lines are in place when this word is
-#else
       __syncthreads();                    // B: lines visible
-#endif
       mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
-      if constexpr (DBG == 4) ++sstep;
+      if constexpr (DBG == MX_DBG_STAMPS) ++sstep;
     };
     struct Env {
       const u32* pk;
@@ -664,18 +597,18 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     };
 #pragma unroll 1
     for (int i = 1; i < C::LOOP_LEN; ++i) {
-      if constexpr (DBG != 2) dbl_step_x<C>(T, Env{mypark, 0, 1, false, K::PQ + 2 * pi * K::HS}, odd, emit);
+      if constexpr (DBG != MX_DBG_CONSUMER) dbl_step_x<C>(T, Env{mypark, 0, 1, false, K::PQ + 2 * pi * K::HS}, odd, emit);
       hand_over();
       const int d = C::LOOP_NAF[i];
       if (d != 0) {
-        if constexpr (DBG != 2) add_step_x<C>(T, Env{mypark, 0, 1, d < 0, K::PQ + 2 * pi * K::HS}, odd, emit);
+        if constexpr (DBG != MX_DBG_CONSUMER) add_step_x<C>(T, Env{mypark, 0, 1, d < 0, K::PQ + 2 * pi * K::HS}, odd, emit);
         hand_over();
       }
     }
     if constexpr (C::CURVE_ID == 0) {
 #pragma unroll 1
       for (int s = 0; s < 2; ++s) {
-        if constexpr (DBG != 2) add_step_x<C>(T, Env{mypark, 2 + 2 * s, 3 + 2 * s, false, K::PQ + 2 * pi * K::HS}, odd, emit);
+        if constexpr (DBG != MX_DBG_CONSUMER) add_step_x<C>(T, Env{mypark, 2 + 2 * s, 3 + 2 * s, false, K::PQ + 2 * pi * K::HS}, odd, emit);
         hand_over();
       }
     }
@@ -683,7 +616,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     // Z3 = 2 Y^3 Z (doubling), Z3 = Z la^3 (addition).  A key of order r never gets there; a small-order twist point handed in
     // without the subgroup check does, and the reference refuses such points at construction (curves/bls12_381.go:196-264,
     // curves/altbn128.go:157-179) -- so the verification reports an encoding error instead of an unspecified verdict.
-    if constexpr (DBG == 0) {
+    if constexpr (DBG == MX_DBG_NONE) {
       const bool z_own = sx_is_zero_mod_p<C>(T.Z);
       const bool z_zero = z_own && pair_swap1(z_own ? 1 : 0) != 0;
       if (valid && z_zero && !odd) atomicOr(flags, FLAG_DEGENERATE);
@@ -691,10 +624,6 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
   } else {
     // ---------------------------------------------------------------- consumer: 10 groups x 6 lanes, lane = 10 j + g
     if (rot_mode & 4) __builtin_amdgcn_s_setprio(3);       // the consumer is the long pole of a block's step: let it issue first
-#ifdef MX_PRIO_EXP                                         // development tools only (tools/mb_x60.hip): intermediate priorities in mode bits 5-6
-    if (((rot_mode >> 5) & 3) == 1) __builtin_amdgcn_s_setprio(1);
-    if (((rot_mode >> 5) & 3) == 2) __builtin_amdgcn_s_setprio(2);
-#endif
     const bool live = lane < 60;
     const int cl = live ? lane : lane - 12;                // lanes 60..63 shadow lanes 48..51 (same 16-lane group of a ds_read_b128: broadcast)
     const int g = cl % 10;
@@ -717,102 +646,46 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
     }
     mx_publish<C, NP>(gb, j, fj, live);
     unsigned sq_d = 0, sq_p = 0;
-    int cstep = 0;                        // MX_EXP_FLAGS: line steps folded so far
-    (void)cstep;
     if constexpr (!rx_lazy<C>) mx_sq_split(COOP_SQ_TAB[j], sq_d, sq_p);
     // sq_next (XL): the squaring reads this step's last publish, which therefore forms the xi copies of e_3..e_5 -- the only ux_mulxi of the step
     auto fold_all = [&](bool sq_next) __attribute__((always_inline)) {
-      if constexpr (DBG == 1) {
-#ifdef MX_EXP_FLAGS
-        mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 2));
-        ++cstep;
-#endif
-        return;
-      }
+      if constexpr (DBG == MX_DBG_PRODUCERS) return;
       // unrolled by three on the 29-bit form (same-box A/B at 2^20 pairings: 54.4 -> 54.0 ms; by two 54.3, by six 54.1), rolled on BLS12-381
       // (unrolled by two or three: 86.8 -> 87.2 ms)
 #pragma unroll K::FOLD_UNROLL
       for (int m = 0; m < K::NLINES; ++m) {
         fj = mx_fold<C, NP>(gb, m, j, glo);
-#ifdef MX_EXP_FLAGS
-        if (m == 2) mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 1));                 // the fold's fetches are in LDS's queue ahead of this word
-        if (m == K::NLINES - 1) mx_seq_st(K::SEQ_DW, (u32)(2 * cstep + 2));
-#endif
         mx_publish<C, NP>(gb, j, fj, live, sq_next && m == K::NLINES - 1);
       }
-#ifdef MX_EXP_FLAGS
-      ++cstep;
-#endif
     };
-#ifdef MX_EXP_FLAGS
-    auto lines_ready = [&]() __attribute__((always_inline)) {
-      mx_seq_wait(K::SEQ_DW + 1, cstep + 1);
-      mx_seq_wait(K::SEQ_DW + 2, cstep + 1);
+    // a step's lines: A (the producers may overwrite the previous lines), B (this step's lines are in place)
+    auto wait_lines = [&]() __attribute__((always_inline)) {
+      mx_stamp<DBG>(srec, 16 + 4 * sstep);
+      __syncthreads();                    // A
+      mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
+      mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
+      __syncthreads();                    // B
+      mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
+      if constexpr (DBG == MX_DBG_STAMPS) ++sstep;
     };
-#endif
 #pragma unroll 1
     for (int i = 1; i < C::LOOP_LEN; ++i) {
-#ifndef MX_SQR_LATE
-      if (DBG != 1 && i > 1) {            // f = 1 before the first step.  The squaring needs no line: it goes AHEAD of A (round 6), so that the producers never park for it at B
+      if (DBG != MX_DBG_PRODUCERS && i > 1) {            // f = 1 before the first step.  The squaring needs no line: it goes AHEAD of A (round 6), so that the producers never park for it at B
         if constexpr (rx_lazy<C>) fj = mx_sqr<C, NP>(gb, j);
         else fj = mx_sqr3<C, NP>(gb, sq_d, sq_p);
         mx_publish<C, NP>(gb, j, fj, live);
       }
-#endif
-      mx_stamp<DBG>(srec, 16 + 4 * sstep);
-#ifdef MX_EXP_FLAGS
-      lines_ready();
-#else
-      __syncthreads();                    // A
-#endif
-      mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
-#ifdef MX_SQR_LATE                     // -DMX_SQR_LATE: rounds 3-5, the squaring between A and B (A/B measurements)
-      if (DBG != 1 && i > 1) {
-        if constexpr (rx_lazy<C>) fj = mx_sqr<C, NP>(gb, j);
-        else fj = mx_sqr3<C, NP>(gb, sq_d, sq_p);
-        mx_publish<C, NP>(gb, j, fj, live);
-      }
-#endif
-      mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
-#ifndef MX_EXP_FLAGS
-      __syncthreads();                    // B
-#endif
-      mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
-      if constexpr (DBG == 4) ++sstep;
+      wait_lines();
       fold_all(C::LOOP_NAF[i] == 0 && i + 1 < C::LOOP_LEN);
       if (C::LOOP_NAF[i] != 0) {
-        mx_stamp<DBG>(srec, 16 + 4 * sstep);
-#ifdef MX_EXP_FLAGS
-        lines_ready();
-#else
-        __syncthreads();
-#endif
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
-#ifndef MX_EXP_FLAGS
-        __syncthreads();
-#endif
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
-        if constexpr (DBG == 4) ++sstep;
+        wait_lines();
         fold_all(i + 1 < C::LOOP_LEN);
       }
     }
     if constexpr (C::CURVE_ID == 0) {
 #pragma unroll 1
       for (int s = 0; s < 2; ++s) {
-        mx_stamp<DBG>(srec, 16 + 4 * sstep);
-#ifdef MX_EXP_FLAGS
-        lines_ready();
-#else
-        __syncthreads();
-#endif
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 1);
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 2);
-#ifndef MX_EXP_FLAGS
-        __syncthreads();
-#endif
-        mx_stamp<DBG>(srec, 16 + 4 * sstep + 3);
-        if constexpr (DBG == 4) ++sstep;
+        wait_lines();
         fold_all(false);
       }
     }
@@ -825,15 +698,7 @@ __global__ void __launch_bounds__(192, MX_WAVES) k_miller_x60(const Aff<F1<C>>* 
       out[((size_t)blockIdx.x * 10 + g) * 6 + j] = r;
     }
   }
-  if constexpr (DBG == 3) {
-    if (lane == 0) {
-      u32* rec = rec_dbg + ((size_t)blockIdx.x * 3 + w) * 8;
-      const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-      rec[4] = (u32)t; rec[5] = (u32)(t >> 32);
-      rec[6] = (u32)role;
-    }
-  }
-  if constexpr (DBG == 4) {
+  if constexpr (DBG == MX_DBG_STAMPS) {
     if (srec != nullptr && lane == 0) {
       const unsigned long long t = __builtin_amdgcn_s_memrealtime();
       srec[4] = (u32)t; srec[5] = (u32)(t >> 32);

@@ -1,5 +1,5 @@
 // Development tool (not part of the library): who waits for whom inside k_miller_x60?
-// Runs the kernel's DBG == 4 form (miller_x.hpp: s_memtime stamps at the arrival at and the release from the two block barriers of every
+// Runs the kernel's MX_DBG_STAMPS form (miller_x.hpp: s_memtime stamps at the arrival at and the release from the two block barriers of every
 // line step, every sixteenth block) over a whole batch and writes the raw records to a file; tools/stamps_report.py turns them into
 // the per-role histograms of profiles/r6/.  Also times the plain kernel, the consumer-only and the producer-only forms beside it, and
 // the issue rate of v_mad_u64_u32 with ONE, two and three waves per SIMD.
@@ -62,18 +62,18 @@ static void run(const char* name, size_t n, int rot, const std::string& prefix) 
   u32* rec;
   CHK(hipMalloc(&rec, nsamp * 3 * MX_STAMP_DW * 4));
   CHK(hipMemset(rec, 0, nsamp * 3 * MX_STAMP_DW * 4));
-  const double whole = time_kernel<C, 0>(in, n, rot, 3, nullptr);
+  const double whole = time_kernel<C, MX_DBG_NONE>(in, n, rot, 3, nullptr);
   printf("%s whole %.3f ms\n", name, whole); fflush(stdout);
-  {   // the partial products of the plain kernel as one checksum: every build variant must print the same one
+  {   // the partial products of the plain kernel as one checksum: a changed kernel must print the same one
     std::vector<uint8_t> ho(in.nb * 60 * sizeof(Fp2<C>));
     CHK(hipMemcpy(ho.data(), in.out, ho.size(), hipMemcpyDeviceToHost));
     unsigned long long hsh = 1469598103934665603ull;
     for (size_t i = 0; i < ho.size(); ++i) { hsh ^= ho[i]; hsh *= 1099511628211ull; }
     printf("%s partial products checksum %016llx\n", name, hsh);
   }
-  const double prod = time_kernel<C, 1>(in, n, rot, 2, nullptr);
-  const double cons = time_kernel<C, 2>(in, n, rot, 2, nullptr);
-  const double stamped = time_kernel<C, 4>(in, n, rot, 1, rec);      // the records of the LAST launch stay
+  const double prod = time_kernel<C, MX_DBG_PRODUCERS>(in, n, rot, 2, nullptr);
+  const double cons = time_kernel<C, MX_DBG_CONSUMER>(in, n, rot, 2, nullptr);
+  const double stamped = time_kernel<C, MX_DBG_STAMPS>(in, n, rot, 1, rec);      // the records of the LAST launch stay
   printf("%s n=%zu mode=%d  whole %.3f ms   producers only %.3f ms   consumer only %.3f ms   with stamps %.3f ms\n", name, n, rot, whole, prod, cons, stamped);
   std::vector<u32> h(nsamp * 3 * MX_STAMP_DW);
   CHK(hipMemcpy(h.data(), rec, h.size() * 4, hipMemcpyDeviceToHost));

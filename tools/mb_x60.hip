@@ -1,6 +1,6 @@
 // Development microbenchmarks for k_miller_x60 (not part of the library):
 //   * issue cost of the instructions the kernel is made of, relative to v_mad_u64_u32
-//   * the kernel with only one of its two roles doing work (DBG 1 / 2), next to the whole kernel
+//   * the kernel with only one of its two roles doing work (MX_DBG_PRODUCERS / MX_DBG_CONSUMER), next to the whole kernel
 // build:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ibgls_amd/csrc -Iinclude tools/mb_x60.hip -o tools/mb_x60.bin
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -268,12 +268,12 @@ int main(int argc, char** argv) {
     const size_t n = argc > 2 ? (size_t)atol(argv[2]) : 61440;
     for (int a = 3; a < (argc > 3 ? argc : 4); ++a) {
       const int rot = argc > 3 ? atoi(argv[a]) : 0;
-      printf("BLS381 n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms\n", n, rot, time_x60<BLS381, 0>(n, rot, 5), time_x60<BLS381, 1>(n, rot, 3),
-             time_x60<BLS381, 2>(n, rot, 3));
-      printf("BN254  n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms\n", n, rot, time_x60<BN254, 0>(n, rot, 5), time_x60<BN254, 1>(n, rot, 3),
-             time_x60<BN254, 2>(n, rot, 3));
-      printf("BN254W n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms   (nine limbs of 29 bits)\n", n, rot, time_x60<BN254W, 0>(n, rot, 5),
-             time_x60<BN254W, 1>(n, rot, 3), time_x60<BN254W, 2>(n, rot, 3));
+      printf("BLS381 n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms\n", n, rot, time_x60<BLS381, MX_DBG_NONE>(n, rot, 5), time_x60<BLS381, MX_DBG_PRODUCERS>(n, rot, 3),
+             time_x60<BLS381, MX_DBG_CONSUMER>(n, rot, 3));
+      printf("BN254  n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms\n", n, rot, time_x60<BN254, MX_DBG_NONE>(n, rot, 5), time_x60<BN254, MX_DBG_PRODUCERS>(n, rot, 3),
+             time_x60<BN254, MX_DBG_CONSUMER>(n, rot, 3));
+      printf("BN254W n=%zu mode=%d  whole %.3f ms   producer only %.3f ms   consumer only %.3f ms   (nine limbs of 29 bits)\n", n, rot, time_x60<BN254W, MX_DBG_NONE>(n, rot, 5),
+             time_x60<BN254W, MX_DBG_PRODUCERS>(n, rot, 3), time_x60<BN254W, MX_DBG_CONSUMER>(n, rot, 3));
     }
   }
   return 0;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turns the raw barrier stamps of tools/mb_stamps.bin (k_miller_x60, DBG == 4) into the per-role table and histograms of profiles/r6/.
+"""Turns the raw barrier stamps of tools/mb_stamps.bin (k_miller_x60, MX_DBG_STAMPS) into the per-role table and histograms of profiles/r6/.
 
 For every sampled block and line step s the three waves record the s_memtime clock at: arrival at barrier A, release from A, arrival at B,
 release from B.  From those:
