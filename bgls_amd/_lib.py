@@ -48,6 +48,8 @@ SIGNATURES = {
     "bgls_rlc_coefficients": (ci, [u8p, sz, u8p]),
     "bgls_bb_verify_batch": (ci, [ci, u8p, u8p, u8p, u8p, sz, u8p, u8p]),
     "bgls_bb_verify_batch_dev": (ci, [ci, vp, vp, vp, vp, sz, u8p, u8p, vp]),
+    "bgls_bb_verify_batch_combined": (ci, [ci, u8p, u8p, u8p, u8p, sz, u64p, sz, u8p, u8p, u8p]),
+    "bgls_bb_verify_batch_combined_dev": (ci, [ci, vp, vp, vp, vp, sz, u64p, sz, u8p, u8p, u8p, vp]),
     "bgls_aggregate_sets": (ci, [ci, ci, u8p, u64p, sz, u8p]),
     "bgls_verify_multi_batch_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, ci, vp]),
     "bgls_verify_multi_batch_submit_dev": (ci, [ci, vp, vp, vp, sz, sz, vp, sz, sz, ci, vp]),

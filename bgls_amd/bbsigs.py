@@ -4,8 +4,10 @@ bgls_bb_verify_batch call for the whole batch (a single Verify is a batch of one
 the group order) and the blake2b-256 message hash of the hashed forms are host work, as in the reference."""
 import ctypes
 import hashlib
+import os
 import secrets
 from . import _lib
+from .bgls import _group_offsets
 from .curves import _reduce_scalar, Point, G1, G2
 
 
@@ -128,6 +130,50 @@ def VerifyBatch(curve, sigs, pks, msgs):
     return _verify_batch(curve, sigs, pks, msgs)
 
 
+def VerifyBatchCombined(curve, sigs, pks, msgs, group=None, seed=None):
+    """"Are these Boneh-Boyen signatures all valid?" under one combined check per group of consecutive items
+    (bgls_bb_verify_batch_combined: the Miller loops of a group share their squarings, one final exponentiation per group instead of one
+    per item).  group: an int chunk size, or None for one group over all items; seed: 32 bytes from a CSPRNG drawn AFTER the inputs are
+    fixed (None draws os.urandom(32)).  Returns the list of group verdicts; a group that holds an item Verify rejects is rejected except
+    with probability about 2^-127.  Every item must be made of Points of this curve; a foreign or nil point, or an encoding error
+    anywhere, raises ValueError (use VerifyBatch to settle such a batch)."""
+    n = len(sigs)
+    if not (n == len(pks) == len(msgs)):
+        raise ValueError("sigs, pks and msgs differ in length")
+    if seed is None:
+        seed = os.urandom(32)
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    if n == 0:
+        return []
+    if not all(_batchable(curve, s, k) for s, k in zip(sigs, pks)):
+        raise ValueError("the combined check takes Signatures and Pubkeys made of G1 / G2 Points of this curve only")
+    goff = _group_offsets(n, group)
+    verdicts = (ctypes.c_uint8 * (len(goff) - 1))()
+    rc = _lib.load().bgls_bb_verify_batch_combined(curve.id, _lib.buf(b"".join(s.Sigma.raw for s in sigs)),
+                                                   _lib.buf(b"".join(_mag(curve, s.R) for s in sigs)),
+                                                   _lib.buf(b"".join(k.U.raw + k.V.raw for k in pks)),
+                                                   _lib.buf(b"".join(_mag(curve, m) for m in msgs)), n,
+                                                   (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1, _lib.buf(bytes(seed)), verdicts, None)
+    if rc < 0:
+        raise ValueError("bgls_bb_verify_batch_combined: %s" % _lib.last_error())
+    return [v == 1 for v in verdicts]
+
+
+def VerifyBatchLocated(curve, sigs, pks, msgs, group=64, seed=None):
+    """One verdict per item at the combined check's cost where everything is valid: ONE combined call over groups of `group` items, then
+    ONE VerifyBatch call over only the items of the rejected groups; the items of accepted groups get True."""
+    n = len(sigs)
+    goff = _group_offsets(n, group)
+    groups = VerifyBatchCombined(curve, sigs, pks, msgs, group, seed)
+    out = [True] * n
+    again = [b for g, ok in enumerate(groups) if not ok for b in range(goff[g], goff[g + 1])]
+    if again:
+        for b, v in zip(again, VerifyBatch(curve, [sigs[b] for b in again], [pks[b] for b in again], [msgs[b] for b in again])):
+            out[b] = v
+    return out
+
+
 def blake2b256(msg, p):                             # bbsigs/hashedbbsigs.go:34-39
     return int.from_bytes(hashlib.blake2b(bytes(msg), digest_size=32).digest(), "big") % p
 
@@ -152,3 +198,15 @@ def VerifyHashedBatch(curve, sigs, pks, msgs):
     """VerifyHashed for a batch: the messages are hashed on the host, the verifications are one call."""
     order = curve.GetG1Order()
     return _verify_batch(curve, sigs, pks, [blake2b256(m, order) for m in msgs])
+
+
+def VerifyHashedBatchCombined(curve, sigs, pks, msgs, group=None, seed=None):
+    """VerifyBatchCombined over hashed messages: blake2b256 on the host, as VerifyHashedBatch."""
+    order = curve.GetG1Order()
+    return VerifyBatchCombined(curve, sigs, pks, [blake2b256(m, order) for m in msgs], group, seed)
+
+
+def VerifyHashedBatchLocated(curve, sigs, pks, msgs, group=64, seed=None):
+    """VerifyBatchLocated over hashed messages: blake2b256 on the host, as VerifyHashedBatch."""
+    order = curve.GetG1Order()
+    return VerifyBatchLocated(curve, sigs, pks, [blake2b256(m, order) for m in msgs], group, seed)

@@ -288,6 +288,25 @@ int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, 
   DISPATCH(curve, bb_verify_dev_t<CV>(d_sigmas, d_rs, d_keys, d_ms, n, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+int bgls_bb_verify_batch_combined(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n,
+                                  const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out) try {
+  if (n == 0) return 0;                                   // before any pointer is looked at, as bgls_bb_verify_batch
+  int rc;
+  if ((rc = rlc_args_ok(group_off, n_groups, n, seed))) return rc;
+  if (!sigmas || !rs || !keys || !ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, bb_verify_combined_t<CV>(sigmas, rs, keys, ms, n, group_off, n_groups, seed, verdicts, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_bb_verify_batch_combined_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n,
+                                      const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out,
+                                      void* stream) try {
+  if (n == 0) return 0;                                   // before any pointer is looked at, as bgls_bb_verify_batch
+  int rc;
+  if ((rc = rlc_args_ok(group_off, n_groups, n, seed))) return rc;
+  if (!d_sigmas || !d_rs || !d_keys || !d_ms || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, bb_verify_combined_dev_t<CV>(d_sigmas, d_rs, d_keys, d_ms, n, group_off, n_groups, seed, verdicts, gt_out, stream));
+} BGLS_ABI_GUARD
+
 int bgls_pairing_product(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) try {
   if (n >= MAX_BATCH) return too_large();
   if (!gt_out || (n && (!g1s || !g2s))) return fail(BGLS_ERR_ARG, "NULL argument");

@@ -511,8 +511,9 @@ struct Engine {
   // d_w16 != nullptr: pair i is (w_i H(m_i), pk_i) with 16-byte big-endian weights, as in miller_product.
   // pre != nullptr (the combined multi-signature check): nothing is hashed or parsed here -- pre->g1s are the n resident G1 points of the
   // pairs (already scaled; uncleared on BLS12-381) and pre->sigs the n_inst resident affine points that take the place of the -sigma_b;
-  // d_sigs, mv and d_w16 are not read.
-  struct PreScaled { const Aff<G1F>* g1s; const Aff<G1F>* sigs; };
+  // d_sigs, mv and d_w16 are not read.  pre->cleared (the combined Boneh-Boyen check): the pre->g1s are G1 points, and the epilogue folds the
+  // signature-slot pair in without raising an instance's rest to the cofactor.
+  struct PreScaled { const Aff<G1F>* g1s; const Aff<G1F>* sigs; bool cleared = false; };
   static int miller_product_batch(Ctx& c, hipStream_t st, const uint8_t* d_sigs, const uint8_t* d_keys, MsgView mv, const uint64_t* inst_off, size_t n_inst,
                                   int check_dups, uint8_t* d_partials, uint32_t* d_iflags, uint32_t* d_flags, const uint8_t* d_w16 = nullptr,
                                   const PreScaled* pre = nullptr) {
@@ -633,7 +634,7 @@ struct Engine {
     const LineCoeffs<C>* gl = nullptr;
     if ((rc = gen_lines(c, &gl))) return rc;
     Scope sc(c, st, ST_EPI);
-    kl::epiloguex_seg<C>(st, n_inst, red, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags);
+    kl::epiloguex_seg<C>(st, n_inst, red, (const Aff<G1F>*)sigs, gl, (Fp2<C>*)epi, d_partials, d_flags, !(pre && pre->cleared));
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -897,11 +898,11 @@ struct Engine {
       return 0;
     }
     int rc;
-    // the epilogue kernels of the throughput shapes always raise a BLS12-381 product to the G1 cofactor: cleared hash points
-    // together with a signature pair would come out as prod^h * e(-sigma, g2) there.  No caller does that (every BLS12-381
-    // verification pairs uncleared points); refuse it rather than return a wrong GT value.
-    if (C::CURVE_ID == 1 && sig && !cofactor && npairs > LAT_MAX)
-      return fail(BGLS_ERR_ARG, "BLS12-381: a signature pair with cleared hash points is only served by the latency shape (<= 128 pairings)");
+    // BLS12-381 G1 points with a signature pair (the combined Boneh-Boyen check): the k_miller_x60 shape folds the pair in with its
+    // epilogue's cofactor power switched off.  The legacy epilogue and the 32-bit fallback shape always raise the product to the
+    // cofactor, and cleared points would come out as prod^h * e(sig, g2) there: refused rather than answered with a wrong GT value.
+    if (C::CURVE_ID == 1 && sig && !cofactor && npairs > LAT_MAX && (legacy(LG_EPI) || !(miller_shape() == 4 || miller_shape() == 0)))
+      return fail(BGLS_ERR_ARG, "BLS12-381: a signature pair with G1 points above 128 pairings is served by the k_miller_x60 shape and its epilogue only");
     const LineCoeffs<C>* gl = nullptr;
     if (sig && (rc = gen_lines(c, &gl))) return rc;
     void *pa, *pb;
@@ -969,7 +970,7 @@ struct Engine {
         HIPCHK(hipGetLastError());
         return 0;
       }
-      return emit_partial(c, st, red, cofactor || sig != nullptr, sig, gl, d_partial);
+      return emit_partial(c, st, red, cofactor || sig != nullptr, sig, gl, d_partial, cofactor);
     }
 #ifdef BGLS_LEGACY_KERNELS
     // shape 5, the 32-bit fallback (k_miller_ab64): 64 pairings per block at 256 registers: one 2^16 batch is exactly 1024 resident blocks; larger batches run as
@@ -1000,9 +1001,9 @@ struct Engine {
   }
 
   // serialise the reduced product; with `epilogue`: raise it to the G1 cofactor (BLS12-381 raw hash points; a no-op
-  // exponent on alt-bn128) and fold the signature pair in on the 36-lane arithmetic
+  // exponent on alt-bn128; not at all with power = false, k_epilogue_ax only) and fold the signature pair in on the 36-lane arithmetic
   static int emit_partial(Ctx& c, hipStream_t st, const Fp2<C>* w, bool epilogue, const Aff<G1F>* sig, const LineCoeffs<C>* gl,
-                          uint8_t* d_partial) {
+                          uint8_t* d_partial, bool power = true) {
     if (!epilogue) {
       kl::w_to_bytes<C>(st, w, d_partial);
     } else {
@@ -1015,7 +1016,7 @@ struct Engine {
       if (!epix) kl::cofactor_epilogue<C>(st, w, sig, gl, d_partial);
       else
 #endif
-      kl::cofactor_epiloguex<C>(st, w, sig, gl, (Fp2<C>*)tmp, d_partial, nullptr);
+      kl::cofactor_epiloguex<C>(st, w, sig, gl, (Fp2<C>*)tmp, d_partial, nullptr, power);
     }
     HIPCHK(hipGetLastError());
     return 0;

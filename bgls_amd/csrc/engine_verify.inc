@@ -628,6 +628,93 @@ int bb_verify_dev_t(const void* d_sigmas, const void* d_rs, const void* d_keys, 
   return bb_verify_run<C>(k.c, k.st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
 }
 
+// ---- the combined check for Boneh-Boyen signatures: one random linear combination per group (bgls_bb_verify_batch_combined) ----
+// n Boneh-Boyen items under ONE check per group of consecutive items: with rho_b the coefficients of bgls_rlc_coefficients and
+// s_g = sum of rho_b over group g as a plain integer, verdict g = [ prod_b e(rho_b sigma_b, Q_b) * e(-s_g g1, g2) == 1 ] over the items b of
+// group g, Q_b = m_b g2 + U_b + r_b V_b.  Each stage once per call: the parse of the sigma_b; k_bb_keys (ST_BB_KEYS: Q_b as wire bytes, no
+// reference pair); then under ST_RLC the coefficients (root on the host, k_blake2x_expand, k_bb_rlc_odd), rho_b sigma_b in place
+// (k_scale_g1_inplace), the sums s_g (k_bb_rlc_sums), s_g g1 from the fixed-base table of g1 (k_fb_scale) and its parse with negation
+// into the signature slots; Engine::miller_product_batch over the groups as instances on the pre-scaled points -- or, with one group,
+// Engine::miller on the same resident points, so that a single big group takes the unpadded 64-form -- both WITHOUT the cofactor power of
+// their BLS12-381 epilogues (sigma_b is a G1 point, not an uncleared hash point); batch_verdicts_run's tail over n_groups items.
+// Slots (one live buffer each): WS_G1S n + 2 points (sigma_b, then rho_b sigma_b; one group: -s g1 at index n), WS_SEG_KEYS the Q_b,
+// WS_RLC_OFF the XOF root and the n_groups + 1 group offsets, WS_HAE_T the coefficients, WS_RLC_SUMS the n_groups magnitudes s_g,
+// WS_RLC_SIGS the n_groups points s_g g1 as wire bytes, WS_BATCH_SIGS the n_groups signature-slot points; beside them the slots of
+// batch_verdicts_run (WS_BATCH_RES, WS_PART) and of the Miller stage called.
+// group_off: n_groups + 1 HOST offsets or nullptr (one group), already checked (rlc_args_ok).
+template <class C>
+int bb_verify_combined_run(Ctx& c, hipStream_t st, const uint8_t* d_sigmas, const uint8_t* d_rs, const uint8_t* d_keys, const uint8_t* d_ms, size_t n,
+                           const uint64_t* group_off, size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  typedef Aff<F1<C>> A1;
+  // host words on their way to WS_RLC_OFF in one copy: the XOF root, then the n_groups + 1 group offsets (alive until the tail has synchronised)
+  std::vector<uint64_t> tab(8 + n_groups + 1, 0);
+  rlc_root(seed, n, tab.data());
+  uint64_t* goff = tab.data() + 8;
+  for (size_t g = 0; g <= n_groups; ++g) goff[g] = group_off ? group_off[g] : (g ? n : 0);
+  return batch_verdicts_run<C>(c, st, n_groups, {verdicts, gt_out}, [&](uint8_t* d_part, uint32_t* d_iflags, uint32_t* d_flags) {
+    int rc;
+    void *g1s, *qs, *d_tab, *d_r, *d_sums, *d_sg, *sigs;
+    const void *fb1, *fb2;
+    if ((rc = c.get(WS_G1S, (n + 2) * sizeof(A1), &g1s))) return rc;
+    if ((rc = c.get(WS_SEG_KEYS, (n + 1) * E::G2B, &qs))) return rc;
+    if ((rc = c.get(WS_HAE_T, n * 16, &d_r))) return rc;
+    if ((rc = c.get(WS_RLC_SUMS, (n_groups + 1) * 32, &d_sums))) return rc;
+    if ((rc = c.get(WS_RLC_SIGS, (n_groups + 1) * E::G1B, &d_sg))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n_groups + 1) * sizeof(A1), &sigs))) return rc;
+    if (n_groups == 1) sigs = (A1*)g1s + n;                  // Engine::miller wants the signature-slot point behind the pairs' points
+    if ((rc = fixed_base_table<C>(c, BGLS_G1, &fb1))) return rc;
+    if ((rc = fixed_base_table<C>(c, BGLS_G2, &fb2))) return rc;
+    kl::g1_parse<C>(st, d_sigmas, n, 0, (A1*)g1s, d_flags);
+    {
+      Scope sc(c, st, ST_BB_KEYS);
+      kl::bb_keys<C>(st, d_keys, d_rs, d_ms, fb2, n, (uint8_t*)qs, (A1*)g1s, nullptr, d_flags, false);
+      HIPCHK(hipGetLastError());
+    }
+    {
+      Scope sc(c, st, ST_RLC);
+      if ((rc = c.put(st, WS_RLC_OFF, tab.data(), tab.size() * 8, &d_tab))) return rc;
+      kl::blake2x_expand(st, (const uint64_t*)d_tab, (uint32_t)(16 * n), (uint8_t*)d_r);
+      kl::bb_rlc_odd(st, (uint8_t*)d_r, n);
+      kl::scale_g1_inplace<C>(st, (A1*)g1s, (const uint8_t*)d_r, n);                               // rho_b sigma_b
+      kl::bb_rlc_sums(st, (const uint8_t*)d_r, (const uint64_t*)d_tab + 8, n_groups, (uint8_t*)d_sums);
+      kl::fb_scale<C>(st, BGLS_G1, fb1, (const uint8_t*)d_sums, n_groups, (uint8_t*)d_sg);       // s_g g1
+      kl::g1_parse<C>(st, (const uint8_t*)d_sg, n_groups, 1, (A1*)sigs, d_flags);                  // -s_g g1
+      HIPCHK(hipGetLastError());
+    }
+    if (n_groups == 1) return E::miller(c, st, (const A1*)g1s, (const uint8_t*)qs, n, (const A1*)sigs, d_part, d_flags, false);
+    const typename E::PreScaled pre = {(const A1*)g1s, (const A1*)sigs, true};
+    return E::miller_product_batch(c, st, nullptr, (const uint8_t*)qs, MsgView{}, goff, n_groups, 0, d_part, d_iflags, d_flags, nullptr, &pre);
+  });
+}
+
+template <class C>
+int bb_verify_combined_t(const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n, const uint64_t* group_off,
+                         size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  void *d_sigmas, *d_rs, *d_keys, *d_ms;
+  if ((rc = c.put(st, WS_IN_A, sigmas, n * E::G1B, &d_sigmas))) return rc;
+  if ((rc = c.put(st, WS_IN_B, rs, n * 32, &d_rs))) return rc;
+  if ((rc = c.put(st, WS_IN_C, keys, n * 2 * E::G2B, &d_keys))) return rc;
+  if ((rc = c.put(st, WS_IN_D, ms, n * 32, &d_ms))) return rc;
+  return bb_verify_combined_run<C>(c, st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, group_off,
+                                   n_groups, seed, verdicts, gt_out);
+}
+
+template <class C>
+int bb_verify_combined_dev_t(const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n, const uint64_t* group_off,
+                             size_t n_groups, const uint8_t* seed, uint8_t* verdicts, uint8_t* gt_out, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return bb_verify_combined_run<C>(k.c, k.st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n,
+                                   group_off, n_groups, seed, verdicts, gt_out);
+}
+
 template <class C>
 int verify_multi_t(const uint8_t* sig, const uint8_t* keys, size_t n, const uint8_t* msg, size_t msg_len) {
   typedef Engine<C> E;

@@ -33,11 +33,11 @@ __device__ __forceinline__ int bb_scalar_words(const uint8_t* s, u32 (&k)[8]) {
 
 template <class C>
 __global__ void __launch_bounds__(64) k_bb_keys(const uint8_t* keys, const uint8_t* rs, const uint8_t* ms, const Aff<F2<C>>* fb, size_t n, uint8_t* q_out,
-                                                Aff<F1<C>>* g1s, Aff<F1<C>>* nosig, uint32_t* flags) {
+                                                Aff<F1<C>>* g1s, Aff<F1<C>>* nosig, uint32_t* flags, bool ref_pair) {
   typedef F2<C> F;
   constexpr size_t G2B = 4 * C::FP_BYTES;
   const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-  if (i > n) return;
+  if (i > n || (i == n && !ref_pair)) return;
   if (nosig) nosig[i] = Aff<F1<C>>{fp_zero<C>(), fp_zero<C>(), true};       // alt-bn128: no generator pair in k_miller_sets
   if (i == n) {
     g1s[n] = Aff<F1<C>>{fp_load<C>(C::G1X), fp_load<C>(C::G1Y), false};
@@ -95,8 +95,8 @@ __global__ void __launch_bounds__(64) k_bb_verdicts(const uint8_t* gt, size_t n,
 namespace kl {
 template <class C>
 void bb_keys(hipStream_t st, const uint8_t* keys, const uint8_t* rs, const uint8_t* ms, const void* fb_g2, size_t n, uint8_t* q_out, Aff<F1<C>>* g1s,
-             Aff<F1<C>>* nosig, uint32_t* flags) {
-  k_bb_keys<C><<<nblk(n + 1, 64), 64, 0, st>>>(keys, rs, ms, (const Aff<F2<C>>*)fb_g2, n, q_out, g1s, nosig, flags);
+             Aff<F1<C>>* nosig, uint32_t* flags, bool ref_pair) {
+  k_bb_keys<C><<<nblk(n + 1, 64), 64, 0, st>>>(keys, rs, ms, (const Aff<F2<C>>*)fb_g2, n, q_out, g1s, nosig, flags, ref_pair);
 }
 template <class C>
 void bb_w_bytes(hipStream_t st, const Fp2<C>* w, size_t n, uint8_t* out) {
@@ -108,7 +108,7 @@ void bb_verdicts(hipStream_t st, const uint8_t* gt, size_t n, uint32_t* verdicts
 }
 #define BGLS_BB_INST(C)                                                                                                                     \
   template void bb_keys<C>(hipStream_t, const uint8_t*, const uint8_t*, const uint8_t*, const void*, size_t, uint8_t*, Aff<F1<C>>*, Aff<F1<C>>*, \
-                           uint32_t*);                                                                                                      \
+                           uint32_t*, bool);                                                                                                \
   template void bb_w_bytes<C>(hipStream_t, const Fp2<C>*, size_t, uint8_t*);                                                                \
   template void bb_verdicts<C>(hipStream_t, const uint8_t*, size_t, uint32_t*);
 BGLS_BB_INST(BN254)

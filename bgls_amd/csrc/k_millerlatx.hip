@@ -331,7 +331,9 @@ __global__ void __launch_bounds__(64 * (AW + 1)) k_miller_latx(const Aff<F1<C>>*
 // first_role: the role of block 0.  A launch of two blocks (first_role 0) runs both chains side by side; a launch of ONE block runs
 // the signature pair alone (first_role 0) -- it depends on nothing but sigma, so a verification with the machine to itself walks
 // it on the context's side stream while the messages are hashed -- or rest^h alone (first_role 1).
-template <class C, int AW>
+// POW = false: rest is the product over G1 points already (no uncleared hash point among them) and is NOT raised to the cofactor: the
+// second chain only hands rest over.
+template <class C, int AW, bool POW = true>
 __global__ void __launch_bounds__(AW == 2 ? 256 : 128) k_epilogue_ax(const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp,
                                                                      uint32_t* flags, int first_role) {
   typedef FX<C> E;
@@ -355,7 +357,7 @@ __global__ void __launch_bounds__(AW == 2 ? 256 : 128) k_epilogue_ax(const Fp2<C
     }
     __syncthreads();
     int res = S_BASE;
-    if constexpr (C::CURVE_ID == 1) {
+    if constexpr (C::CURVE_ID == 1 && POW) {
       fx_pow<C>(S_ACC, S_BASE, C::COFACTOR, C::COFACTOR_BITS, S_SQ);
       res = S_ACC;
     }
@@ -376,7 +378,7 @@ __global__ void __launch_bounds__(AW == 2 ? 256 : 128) k_epilogue_ax(const Fp2<C
   }
   if (AW == 2 && lane == 63) fx_mul2w_init<C>();
   if constexpr (AW == 2) __syncthreads(); else wave_sync();
-  if constexpr (C::CURVE_ID == 1) {
+  if constexpr (C::CURVE_ID == 1 && POW) {
     u32 epoch = 0;
     auto mul = [&](int dst, int a, int b) {
       if constexpr (AW == 2) fx_mul2w<C>(dst, a, b, ++epoch);
@@ -464,8 +466,8 @@ __global__ void __launch_bounds__(128) k_reduce_fx_seg(const Fp2<C>* in, const u
 
 // k_epilogue_ax over a batch: blocks 2b and 2b + 1 are instance b's two chains -- the signature pair (-sigma_b, g2) on the generator's
 // lines into tmp[12 b ..], and rest_b^h (rest: one reduced partial per instance) into tmp[12 b + 6 ..] -- as the two blocks of the
-// single form with first_role 0.
-template <class C>
+// single form with first_role 0.  POW = false: no cofactor power, as in the single form.
+template <class C, bool POW = true>
 __global__ void __launch_bounds__(256) k_epilogue_ax_seg(const Fp2<C>* rest, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp,
                                                          uint32_t* flags) {
   typedef FX<C> E;
@@ -483,7 +485,7 @@ __global__ void __launch_bounds__(256) k_epilogue_ax_seg(const Fp2<C>* rest, con
   }
   __syncthreads();
   int res = S_BASE;
-  if constexpr (C::CURVE_ID == 1) {
+  if constexpr (C::CURVE_ID == 1 && POW) {
     fx_pow<C>(S_ACC, S_BASE, C::COFACTOR, C::COFACTOR_BITS, S_SQ);
     res = S_ACC;
   }
@@ -521,15 +523,20 @@ void reduce_fx_seg(hipStream_t st, const Fp2<C>* in, const uint32_t* seg, size_t
 }
 template <class C>
 void epiloguex_seg(hipStream_t st, size_t n_inst, const Fp2<C>* rest, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out,
-                   uint32_t* flags) {
-  k_epilogue_ax_seg<C><<<(unsigned)(2 * n_inst), 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sigs, gen_lines, tmp, flags);
+                   uint32_t* flags, bool power) {
+  constexpr bool has_power = C::CURVE_ID == 1;              // alt-bn128: the cofactor is one, one kernel serves both
+  if constexpr (has_power) {
+    if (!power) k_epilogue_ax_seg<C, false><<<(unsigned)(2 * n_inst), 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sigs, gen_lines, tmp, flags);
+  }
+  if (power || !has_power) k_epilogue_ax_seg<C><<<(unsigned)(2 * n_inst), 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sigs, gen_lines, tmp, flags);
   k_epilogue_bx_seg<C><<<(unsigned)n_inst, 64, FX<C>::LDS_BYTES, st>>>(tmp, out);
 }
 template void reduce_fx_seg<BN254>(hipStream_t, const Fp2<BN254>*, const uint32_t*, size_t, Fp2<BN254>*);
 template void reduce_fx_seg<BLS381>(hipStream_t, const Fp2<BLS381>*, const uint32_t*, size_t, Fp2<BLS381>*);
-template void epiloguex_seg<BN254>(hipStream_t, size_t, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*, uint32_t*);
+template void epiloguex_seg<BN254>(hipStream_t, size_t, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*, uint32_t*,
+                                   bool);
 template void epiloguex_seg<BLS381>(hipStream_t, size_t, const Fp2<BLS381>*, const Aff<F1<BLS381>>*, const LineCoeffs<BLS381>*, Fp2<BLS381>*, uint8_t*,
-                                    uint32_t*);
+                                    uint32_t*, bool);
 template <class C>
 void reduce_fx(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* out) {
   const size_t nout = (count + R - 1) / R;
@@ -540,13 +547,17 @@ template void reduce_fx<BLS381>(hipStream_t, const Fp2<BLS381>*, size_t, int, Fp
 static_assert(FX<BN254>::LDS_BYTES_PAIR >= FX<BN254>::LDS_BYTES + FX2W_EXTRA_BYTES, "the pair scratch covers the hand-over words");
 template <class C>
 static void launch_epilogue_ax(hipStream_t st, unsigned blocks, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint32_t* flags,
-                               int first_role) {
-  k_epilogue_ax<C, 2><<<blocks, 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sig, gen_lines, tmp, flags, first_role);
+                               int first_role, bool power = true) {
+  constexpr bool has_power = C::CURVE_ID == 1;              // alt-bn128: the cofactor is one, one kernel serves both
+  if constexpr (has_power) {
+    if (!power) k_epilogue_ax<C, 2, false><<<blocks, 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sig, gen_lines, tmp, flags, first_role);
+  }
+  if (power || !has_power) k_epilogue_ax<C, 2><<<blocks, 256, FX<C>::LDS_BYTES_PAIR, st>>>(rest, sig, gen_lines, tmp, flags, first_role);
 }
 template <class C>
 void cofactor_epiloguex(hipStream_t st, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out,
-                        uint32_t* flags) {
-  launch_epilogue_ax<C>(st, 2, rest, sig, gen_lines, tmp, flags, 0);
+                        uint32_t* flags, bool power) {
+  launch_epilogue_ax<C>(st, 2, rest, sig, gen_lines, tmp, flags, 0, power);
   k_epilogue_bx<C><<<1, 64, FX<C>::LDS_BYTES, st>>>(tmp, out);
 }
 // the two chains as separate launches: part 1 = the signature pair only (tmp[0..5]), part 2 = rest^h (tmp[6..11]) and the product
@@ -561,8 +572,8 @@ void cofactor_epiloguex_part(hipStream_t st, int part, const Fp2<C>* rest, const
 }
 template void cofactor_epiloguex_part<BN254>(hipStream_t, int, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*);
 template void cofactor_epiloguex_part<BLS381>(hipStream_t, int, const Fp2<BLS381>*, const Aff<F1<BLS381>>*, const LineCoeffs<BLS381>*, Fp2<BLS381>*, uint8_t*);
-template void cofactor_epiloguex<BN254>(hipStream_t, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*, uint32_t*);
-template void cofactor_epiloguex<BLS381>(hipStream_t, const Fp2<BLS381>*, const Aff<F1<BLS381>>*, const LineCoeffs<BLS381>*, Fp2<BLS381>*, uint8_t*, uint32_t*);
+template void cofactor_epiloguex<BN254>(hipStream_t, const Fp2<BN254>*, const Aff<F1<BN254>>*, const LineCoeffs<BN254>*, Fp2<BN254>*, uint8_t*, uint32_t*, bool);
+template void cofactor_epiloguex<BLS381>(hipStream_t, const Fp2<BLS381>*, const Aff<F1<BLS381>>*, const LineCoeffs<BLS381>*, Fp2<BLS381>*, uint8_t*, uint32_t*, bool);
 template <class C>
 void miller_latx(hipStream_t st, const Aff<F1<C>>* g1s, const uint8_t* g2s, size_t n, long long sig_at, const LineCoeffs<C>* gen_lines, Fp2<C>* out,
                  uint32_t* flags) {

@@ -97,13 +97,20 @@ template <class C> size_t miller_sets_per_block();
 
 // ---- k_bbsigs.hip: batched Boneh-Boyen verification (bgls_bb_verify_batch).  bb_keys: Q_b = m_b g2 + U_b + r_b V_b as wire bytes to
 // q_out + b G2B for b < n (keys: n x (U || V) wire bytes, rs / ms: n x 32-byte big-endian scalars, fb_g2: the fixed-base table of g2), and
-// the reference pair (g1, g2) at index n: g1s[n], q_out + n G2B; nosig (nullable): n + 1 G1 points at infinity.  bb_w_bytes: n w-basis
-// Miller values (six Fp2 each) to GT bytes.  bb_verdicts: verdicts[b] = (gt[b] == gt[n]) for b < n.
+// the reference pair (g1, g2) at index n: g1s[n], q_out + n G2B; nosig (nullable): n + 1 G1 points at infinity.  ref_pair = false (the
+// combined check): index n is not written, g1s is not read.  bb_w_bytes: n w-basis Miller values (six Fp2 each) to GT bytes.
+// bb_verdicts: verdicts[b] = (gt[b] == gt[n]) for b < n.
 template <class C>
 void bb_keys(hipStream_t st, const uint8_t* keys, const uint8_t* rs, const uint8_t* ms, const void* fb_g2, size_t n, uint8_t* q_out, Aff<F1<C>>* g1s,
-             Aff<F1<C>>* nosig, uint32_t* flags);
+             Aff<F1<C>>* nosig, uint32_t* flags, bool ref_pair = true);
 template <class C> void bb_w_bytes(hipStream_t st, const Fp2<C>* w, size_t n, uint8_t* out);
 template <class C> void bb_verdicts(hipStream_t st, const uint8_t* gt, size_t n, uint32_t* verdicts);
+
+// ---- k_bbrlc.hip: the coefficients of the combined Boneh-Boyen check (bgls_bb_verify_batch_combined; body: bb_rlc.hpp).  bb_rlc_odd: the
+// lowest bit of each of the n 16-byte coefficients set in place.  bb_rlc_sums: out + 32 g <- the sum of the coefficients group_off[g] ..
+// group_off[g + 1] (device offsets) as a 32-byte big-endian magnitude, one wave per group; r16 is 16-byte aligned.
+void bb_rlc_odd(hipStream_t st, uint8_t* r16, size_t n);
+void bb_rlc_sums(hipStream_t st, const uint8_t* r16, const uint64_t* group_off, size_t n_groups, uint8_t* out);
 
 // ---- k_haesets.hip: batched hashed aggregation exponents and weighted key sums (bgls_verify_multi_hae_sets).  hae_root_seg: the BLAKE2Xb
 // root of every set with 1 .. host_min keys to roots + 8 b (keys: wire bytes of g2b each, key_off: n_sets + 1 device offsets), and the
@@ -164,7 +171,9 @@ void miller_latx(hipStream_t st, const Aff<F1<C>>* g1s, const uint8_t* g2s, size
                 uint32_t* flags);
 template <class C> void gt_pow(hipStream_t st, const uint8_t* gt_in, const uint8_t* k_be32, int negate, uint8_t* gt_out, uint32_t* flags);
 template <class C> void cofactor_epilogue(hipStream_t st, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, uint8_t* out);
-template <class C> void cofactor_epiloguex(hipStream_t st, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out, uint32_t* flags);
+// power = false: rest is not raised to the cofactor (its pairs held G1 points, not uncleared hash points); the signature pair is folded in all the same
+template <class C> void cofactor_epiloguex(hipStream_t st, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out, uint32_t* flags,
+                                           bool power = true);
 
 }  // namespace kl
 }  // namespace bgls

@@ -29,10 +29,11 @@ template <class C> void rlc_pair(hipStream_t st, Aff<F1<C>>* hs, const uint8_t* 
 template <class C> void reduce_fx(hipStream_t st, const Fp2<C>* in, size_t count, int R, Fp2<C>* out);
 // segmented form: out[G] = prod in[seg[2G] .. seg[2G] + seg[2G + 1]) for G < nout (an empty segment gives one)
 template <class C> void reduce_fx_seg(hipStream_t st, const Fp2<C>* in, const uint32_t* seg, size_t nout, Fp2<C>* out);
-// the epilogue of n_inst instances: rest[6 b ..] ^ h times the signature pair (sigs[b], g2), GT bytes to out + b GTB; tmp: 12 n_inst Fp2
+// the epilogue of n_inst instances: rest[6 b ..] ^ h times the signature pair (sigs[b], g2), GT bytes to out + b GTB; tmp: 12 n_inst Fp2.
+// power = false: rest[6 b ..] itself times the signature pair (the walked pairs held G1 points, not uncleared hash points)
 template <class C>
 void epiloguex_seg(hipStream_t st, size_t n_inst, const Fp2<C>* rest, const Aff<F1<C>>* sigs, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out,
-                   uint32_t* flags);
+                   uint32_t* flags, bool power = true);
 // the verification epilogue's two chains as separate launches (1: the signature pair, 2: rest^h and the product of the two)
 template <class C> void cofactor_epiloguex_part(hipStream_t st, int part, const Fp2<C>* rest, const Aff<F1<C>>* sig, const LineCoeffs<C>* gen_lines, Fp2<C>* tmp, uint8_t* out);
 

@@ -564,4 +564,71 @@ inline std::vector<bool> bb_verify_batch(const curves::CurveSystem* curve, const
   for (size_t i = 0; i < batch.size(); ++i) out[batch[i]] = rc >= 0 && verdicts[i] == 1;
   return out;
 }
+// "Are these Boneh-Boyen signatures all valid?" under one combined check per group of consecutive items (bgls_bb_verify_batch_combined:
+// shared squarings and one final exponentiation per group).  group: items per group, 0 = one group over all items.  seed: 32 bytes from
+// a CSPRNG drawn AFTER the inputs are fixed (empty: drawn from std::random_device here).  One bool per group; ok (nullable) is cleared
+// when the call could not run -- lengths that differ, an item not made of this curve's points or of 32-byte scalars, an encoding error
+// anywhere -- and the list is then all false.
+inline std::vector<bool> bb_verify_batch_combined(const curves::CurveSystem* curve, const std::vector<curves::Point>& sigmas, const std::vector<curves::Bytes>& rs,
+                                                  const std::vector<curves::Point>& us, const std::vector<curves::Point>& vs, const std::vector<curves::Bytes>& ms,
+                                                  size_t group = 0, curves::Bytes seed = curves::Bytes(), bool* ok = nullptr) {
+  const size_t n = sigmas.size();
+  std::vector<uint64_t> goff(1, 0);
+  for (size_t at = 0; at < n;) goff.push_back(at = (group && at + group < n) ? at + group : n);
+  std::vector<bool> out(goff.size() - 1, false);
+  if (ok) *ok = false;
+  if (rs.size() != n || us.size() != n || vs.size() != n || ms.size() != n || (!seed.empty() && seed.size() != 32)) return out;
+  if (seed.empty()) {
+    std::random_device rd;
+    for (int i = 0; i < 32; ++i) seed.push_back((uint8_t)rd());
+  }
+  curves::Bytes sb, rb, kb, mb;
+  for (size_t b = 0; b < n; ++b) {
+    if (sigmas[b].curve != curve || sigmas[b].group != BGLS_G1 || us[b].curve != curve || us[b].group != BGLS_G2 || vs[b].curve != curve ||
+        vs[b].group != BGLS_G2 || rs[b].size() != 32 || ms[b].size() != 32)
+      return out;
+    sb.insert(sb.end(), sigmas[b].raw.begin(), sigmas[b].raw.end());
+    rb.insert(rb.end(), rs[b].begin(), rs[b].end());
+    kb.insert(kb.end(), us[b].raw.begin(), us[b].raw.end());
+    kb.insert(kb.end(), vs[b].raw.begin(), vs[b].raw.end());
+    mb.insert(mb.end(), ms[b].begin(), ms[b].end());
+  }
+  if (ok) *ok = true;
+  if (n == 0) return out;
+  std::vector<uint8_t> verdicts(out.size(), 0);
+  const int rc = bgls_bb_verify_batch_combined(curve->id, sb.data(), rb.data(), kb.data(), mb.data(), n, goff.data(), out.size(), seed.data(), verdicts.data(),
+                                               nullptr);
+  if (rc < 0 && ok) *ok = false;
+  for (size_t g = 0; g < out.size(); ++g) out[g] = rc >= 0 && verdicts[g] == 1;
+  return out;
+}
+// One bool per item at the combined check's cost where everything is valid: ONE combined call over groups of `group` items, then ONE
+// bb_verify_batch call over only the items of the rejected groups; the items of accepted groups get true.  Where the combined call cannot
+// run, every item goes through bb_verify_batch.
+inline std::vector<bool> bb_verify_batch_located(const curves::CurveSystem* curve, const std::vector<curves::Point>& sigmas, const std::vector<curves::Bytes>& rs,
+                                                 const std::vector<curves::Point>& us, const std::vector<curves::Point>& vs, const std::vector<curves::Bytes>& ms,
+                                                 size_t group = 64, curves::Bytes seed = curves::Bytes()) {
+  const size_t n = sigmas.size();
+  bool ok = false;
+  const std::vector<bool> groups = bb_verify_batch_combined(curve, sigmas, rs, us, vs, ms, group, seed, &ok);
+  if (!ok) return bb_verify_batch(curve, sigmas, rs, us, vs, ms);
+  std::vector<bool> out(n, true);
+  std::vector<size_t> again;
+  for (size_t g = 0; g < groups.size(); ++g)
+    if (!groups[g])
+      for (size_t b = g * (group ? group : n); b < n && (group == 0 || b < (g + 1) * group); ++b) again.push_back(b);
+  if (again.empty()) return out;
+  std::vector<curves::Point> s2, u2, v2;
+  std::vector<curves::Bytes> r2, m2;
+  for (size_t b : again) {
+    s2.push_back(sigmas[b]);
+    r2.push_back(rs[b]);
+    u2.push_back(us[b]);
+    v2.push_back(vs[b]);
+    m2.push_back(ms[b]);
+  }
+  const std::vector<bool> settled = bb_verify_batch(curve, s2, r2, u2, v2, m2);
+  for (size_t i = 0; i < again.size(); ++i) out[again[i]] = settled[i];
+  return out;
+}
 }  // namespace bgls

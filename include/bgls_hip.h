@@ -205,6 +205,33 @@ int bgls_rlc_coefficients(const uint8_t seed[32], size_t n, uint8_t* r_out);
  * Returns the number of accepted items (>= 0) or < 0. */
 int bgls_bb_verify_batch(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms,
                          size_t n, uint8_t* verdicts, uint8_t* gt_out);
+/* "Are these n Boneh-Boyen signatures all valid?" under ONE combined check per group of consecutive items: the Miller loops of a group
+ * share their squarings and a group costs one final exponentiation instead of one per item.  Items are laid out exactly as for
+ * bgls_bb_verify_batch.  With the coefficients rho_b of bgls_rlc_coefficients(seed, n) -- 16 bytes big-endian, the lowest bit set; rho_b
+ * belongs to the index b of the item in the call, whatever the grouping -- and s_g = sum of rho_b over the items of group g as a plain
+ * integer (below 2^156, used as an unreduced magnitude, as bgls_scale_generator takes them),
+ *   verdicts[g] = 1  iff  prod_b e(rho_b sigmas[b], Q_b) * e(-s_g g1, g2) = 1  over the items b of group g,  Q_b = m_b g2 + U_b + r_b V_b.
+ * Groups: group_off holds n_groups + 1 HOST offsets into the items, monotone, from 0, ending at n; group_off == NULL with
+ * n_groups == 1 means one group holding all items.  An empty group is accepted, and its GT element is one.  A caller localises a failure
+ * by running bgls_bb_verify_batch over the items of the rejected groups only (the host mirrors' VerifyBatchLocated /
+ * bb_verify_batch_located do).
+ * gt_out: NULL or n_groups GT elements, the product above after the final exponentiation, byte-equal to bgls_pairing_product over the
+ * pairs (rho_b sigmas[b], Q_b) of the group and (-s_g g1, g2).
+ * THE CONTRACT.  A group whose items bgls_bb_verify_batch would all accept is always accepted.  A group holding an item that
+ * bgls_bb_verify_batch rejects is rejected, except with probability about 2^-127 over a seed the adversary cannot predict (128-bit
+ * coefficients, one bit spent on keeping them non-zero).  A group with exactly ONE bad item is rejected with certainty: the product is
+ * then e(g1, g2)^(-rho_b) * e(rho_b sigma_b, Q_b), and rho_b is odd and below the group order.  The seed MUST be drawn from a CSPRNG AFTER
+ * the inputs are fixed and must never be reused where an adversary can see it first: whoever knows the coefficients in advance can shift
+ * two signatures under one Q by +rho_2 D and -rho_1 D and pass.  The equivalence is promised for sigma in G1 and U, V in G2, i.e. Points
+ * constructed through bgls_check_points and its kin; for on-curve points outside the subgroups the verdict is unspecified (the call still
+ * does not fault).  An item with sigma or Q_b at infinity contributes e = 1: its group is rejected, as the per-item call rejects the item.
+ * Errors: a non-canonical or off-curve sigma, U or V ANYWHERE, or a degenerate point step, fails the whole call with
+ * BGLS_ERR_ENCODING and leaves verdicts undefined; BGLS_ERR_NO_DEVICE without a device (no CPU fallback).  BGLS_ERR_ARG, checked before
+ * any device work: non-monotone offsets, group_off not from 0 or not ending at n, group_off == NULL with n_groups != 1, a NULL seed, NULL
+ * arrays with n > 0, n at or above 2^28 (the XOF length 16 n is a uint32).  n == 0 returns 0 without touching a pointer.
+ * Returns the number of accepted groups (>= 0) or < 0. */
+int bgls_bb_verify_batch_combined(int curve, const uint8_t* sigmas, const uint8_t* rs, const uint8_t* keys, const uint8_t* ms, size_t n,
+                                  const uint64_t* group_off, size_t n_groups, const uint8_t seed[32], uint8_t* verdicts, uint8_t* gt_out);
 /* AggregatePoints (curves/curve.go:73-121) over n_sets sets in one pass: out[b] = sum of pts[set_off[b] .. set_off[b+1])
  * (an empty set gives the point at infinity).  What the n_sets AggregateKeys calls of blsKosk.go:128-131 cost. */
 int bgls_aggregate_sets(int curve, int group, const uint8_t* pts, const uint64_t* set_off, size_t n_sets, uint8_t* out);
@@ -477,6 +504,11 @@ int bgls_ams_verify_batch_dev(int curve, const void* d_apks, const void* d_agg_k
  * (NULL: the context's stream) before it returns. */
 int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms,
                              size_t n, uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_bb_verify_batch_combined with its items on the device (same layouts), then the HOST words group_off, n_groups and seed (they plan
+ * the launches).  Same contract and return value; synchronises `stream` (NULL: the context's stream) before it returns. */
+int bgls_bb_verify_batch_combined_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n,
+                                      const uint64_t* group_off, size_t n_groups, const uint8_t seed[32], uint8_t* verdicts,
+                                      uint8_t* gt_out, void* stream);
 /* bgls_verify_aggregate_batch with signatures, keys and messages on the device: d_sigs = n_inst G1 points, d_keys = inst_off[n_inst]
  * G2 points, message i at d_msgs + i * msg_stride (msg_len bytes).  inst_off stays a HOST array (it plans the launches).  Same
  * semantics and return value; synchronises `stream` (NULL: the context's stream) before it returns.  Every batch runs the Miller
