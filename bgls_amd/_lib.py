@@ -92,6 +92,10 @@ SIGNATURES = {
     "bgls_verify_aggregate_h_gt": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, ci, u8p]),
     "bgls_generator": (ci, [ci, ci, u8p]),
     "bgls_pair": (ci, [ci, u8p, u8p, u8p]),
+    "bgls_pair_batch": (ci, [ci, u8p, u8p, sz, u8p]),
+    "bgls_pair_batch_dev": (ci, [ci, vp, vp, sz, vp, vp]),
+    "bgls_final_exp_batch": (ci, [ci, u8p, sz, u8p, u8p]),
+    "bgls_final_exp_batch_dev": (ci, [ci, vp, sz, vp, vp, vp]),
     "bgls_gt_mul": (ci, [ci, u8p, u8p, u8p]),
     "bgls_gt_pow": (ci, [ci, u8p, u8p, ci, u8p]),
     "bgls_gt_identity": (ci, [ci, u8p]),

@@ -307,6 +307,34 @@ int bgls_bb_verify_batch_combined_dev(int curve, const void* d_sigmas, const voi
   DISPATCH(curve, bb_verify_combined_dev_t<CV>(d_sigmas, d_rs, d_keys, d_ms, n, group_off, n_groups, seed, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+int bgls_final_exp_batch(int curve, const uint8_t* gt_in, size_t n, uint8_t* gt_out, uint8_t* is_one) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!gt_in || (!gt_out && !is_one)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, final_exp_batch_t<CV>(gt_in, n, gt_out, is_one));
+} BGLS_ABI_GUARD
+
+int bgls_final_exp_batch_dev(int curve, const void* d_gt_in, size_t n, void* d_gt_out, void* d_is_one, void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!d_gt_in || (!d_gt_out && !d_is_one)) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, final_exp_batch_dev_t<CV>(d_gt_in, n, d_gt_out, d_is_one, stream));
+} BGLS_ABI_GUARD
+
+int bgls_pair_batch(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!g1s || !g2s || !gt_out) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, pair_batch_t<CV>(g1s, g2s, n, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_pair_batch_dev(int curve, const void* d_g1s, const void* d_g2s, size_t n, void* d_gt_out, void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!d_g1s || !d_g2s || !d_gt_out) return fail(BGLS_ERR_ARG, "NULL argument");
+  DISPATCH(curve, pair_batch_dev_t<CV>(d_g1s, d_g2s, n, d_gt_out, stream));
+} BGLS_ABI_GUARD
+
 int bgls_pairing_product(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) try {
   if (n >= MAX_BATCH) return too_large();
   if (!gt_out || (n && (!g1s || !g2s))) return fail(BGLS_ERR_ARG, "NULL argument");

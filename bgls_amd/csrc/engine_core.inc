@@ -805,6 +805,31 @@ struct Engine {
     return 0;
   }
 
+  // A batch of n independent pairings (bgls_pair_batch): item b is (P_b, Q_b) = (d_g1s[b], d_g2s[b]) as wire bytes.  Engine::miller_bb's
+  // Miller stage without its keys and its reference pair: the parse of the P_b, one k_miller_sets launch sequence with P_b in the
+  // hash-point slot and Q_b in the key-sum slot (alt-bn128: every signature slot at infinity; BLS12-381: the w-basis value straight to
+  // bytes, no cofactor power), writing n GT partials (bytes, no final exponentiation) to d_partials.
+  static int miller_pairs(Ctx& c, hipStream_t st, const uint8_t* d_g1s, const uint8_t* d_g2s, size_t n, uint8_t* d_partials, uint32_t* d_flags) {
+    if (n >= MAX_BATCH) return too_large();
+    constexpr bool bls = C::CURVE_ID == 1;
+    void *g1s, *nosig, *rest = nullptr;
+    int rc;
+    if ((rc = c.get(WS_G1S, (n + 1) * sizeof(Aff<G1F>), &g1s))) return rc;
+    if ((rc = c.get(WS_BATCH_SIGS, (n + 1) * sizeof(Aff<G1F>), &nosig))) return rc;
+    if (bls && (rc = c.get(WS_F_A, (n + 1) * 6 * sizeof(Fp2<C>), &rest))) return rc;
+    const LineCoeffs<C>* gl = nullptr;
+    if ((rc = gen_lines(c, &gl))) return rc;
+    kl::g1_parse<C>(st, d_g1s, n, 0, (Aff<G1F>*)g1s, d_flags);
+    if (!bls) kl::g1_inf_fill<C>(st, (Aff<G1F>*)nosig, n);
+    if ((rc = miller_sets(c, st, (const Aff<G1F>*)g1s, d_g2s, (const Aff<G1F>*)nosig, gl, n, (Fp2<C>*)rest, d_partials, d_flags))) return rc;
+    if (bls) {
+      Scope sc(c, st, ST_EPI);
+      kl::bb_w_bytes<C>(st, (const Fp2<C>*)rest, n, d_partials);
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
+
   // H(m_i) as affine Montgomery points.  raw (BLS12-381 only): points before cofactor clearing, for the cofactor-in-GT
   // verification path (DESIGN.md section 3).
   static int hash_to_g1(Ctx& c, hipStream_t st, MsgView mv, size_t n, Aff<G1F>* out, uint32_t* d_flags, bool raw = false) {

@@ -628,6 +628,105 @@ int bb_verify_dev_t(const void* d_sigmas, const void* d_rs, const void* d_keys, 
   return bb_verify_run<C>(k.c, k.st, (const uint8_t*)d_sigmas, (const uint8_t*)d_rs, (const uint8_t*)d_keys, (const uint8_t*)d_ms, n, verdicts, gt_out);
 }
 
+// ---- one GT element per item: n final exponentiations, n pairings (bgls_final_exp_batch, bgls_pair_batch) ----
+// Where the n GT elements and the n "is one" marks of gt_values_run go: device pointers (dev: the caller's, written by the launches) or
+// host pointers (copied out only after the call's flag word has come back clear, so a failed call leaves them as they were).
+struct GtOut {
+  uint8_t* gt;                       // nullable (not both)
+  uint8_t* is_one;                   // nullable
+  bool dev;
+};
+
+// stage(d_part, d_flags) leaves one GT partial per item at d_part (WS_PART, n GT elements; encoding failures in d_flags, zeroed here), or
+// nothing where d_in is the caller's own n partials; then one final exponentiation per item in ONE launch of the throughput kernel
+// k_finalxt_batch (ST_FINAL; ten items per wave, finalxt.hpp -- batch_verdicts_run above still finishes on k_finalx_batch).
+// Words at WS_BATCH_RES: n per-item flags (zero: nothing refuses an item here), n marks of the final exponentiation, the call's flag word.
+// Synchronises st.  Returns 0 or the code of the flag word.
+template <class C, class Stage>
+int gt_values_run(Ctx& c, hipStream_t st, size_t n, const uint8_t* d_in, const GtOut& out, Stage&& stage) {
+  typedef Engine<C> E;
+  if (c.res_pending) return in_flight();
+  const bool host_gt = out.gt && !out.dev;
+  void *d_res, *d_part = nullptr, *d_gt = out.dev ? out.gt : nullptr;
+  int rc;
+  if ((rc = c.get(WS_BATCH_RES, (2 * n + 1) * 4, &d_res))) return rc;
+  if (!d_in && (rc = c.get(WS_PART, n * E::GTB, &d_part))) return rc;
+  if (host_gt && (rc = c.get(WS_OUT, n * E::GTB, &d_gt))) return rc;
+  uint32_t* d_iflags = (uint32_t*)d_res;
+  uint32_t* d_one = d_iflags + n;
+  uint32_t* d_flags = d_one + n;
+  Drain drain{st};
+  HIPCHK(hipMemsetAsync(d_res, 0, (2 * n + 1) * 4, st));
+  if ((rc = stage((uint8_t*)d_part, d_flags))) return rc;
+  {
+    Scope sc(c, st, ST_FINAL);
+    kl::finalxt_batch<C>(st, d_in ? d_in : (const uint8_t*)d_part, n, (uint8_t*)d_gt, d_one, d_iflags, d_flags);
+  }
+  if (out.dev && out.is_one) kl::is_one_bytes(st, d_one, n, out.is_one);
+  HIPCHK(hipGetLastError());
+  uint32_t flags = 0;
+  HIPCHK(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c.collect();
+  if ((rc = flags_to_rc(flags))) return rc;
+  if (out.dev) {
+    drain.armed = false;
+    return 0;
+  }
+  std::vector<uint32_t> ones(out.is_one ? n : 0);
+  if (out.is_one) HIPCHK(hipMemcpyAsync(ones.data(), d_one, n * 4, hipMemcpyDeviceToHost, st));
+  if (host_gt) HIPCHK(hipMemcpyAsync(out.gt, d_gt, n * E::GTB, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  drain.armed = false;
+  for (size_t b = 0; b < ones.size(); ++b) out.is_one[b] = ones[b] ? 1 : 0;
+  return 0;
+}
+
+template <class C>
+int final_exp_batch_t(const uint8_t* gt_in, size_t n, uint8_t* gt_out, uint8_t* is_one) {
+  Call k;
+  if (k.rc) return k.rc;
+  int rc;
+  void* d_in;
+  if ((rc = k.c.put(k.st, WS_IN_A, gt_in, n * Engine<C>::GTB, &d_in))) return rc;
+  return gt_values_run<C>(k.c, k.st, n, (const uint8_t*)d_in, {gt_out, is_one, false}, [](uint8_t*, uint32_t*) { return 0; });
+}
+
+template <class C>
+int final_exp_batch_dev_t(const void* d_gt_in, size_t n, void* d_gt_out, void* d_is_one, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  return gt_values_run<C>(k.c, k.st, n, (const uint8_t*)d_gt_in, {(uint8_t*)d_gt_out, (uint8_t*)d_is_one, true}, [](uint8_t*, uint32_t*) { return 0; });
+}
+
+// n independent CurveSystem.Pair calls in one set of launches: Engine::miller_pairs, then gt_values_run's tail
+template <class C>
+int pair_batch_t(const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  int rc;
+  void *d_g1s, *d_g2s;
+  if ((rc = c.put(st, WS_IN_A, g1s, n * E::G1B, &d_g1s))) return rc;
+  if ((rc = c.put(st, WS_IN_B, g2s, n * E::G2B, &d_g2s))) return rc;
+  return gt_values_run<C>(c, st, n, nullptr, {gt_out, nullptr, false}, [&](uint8_t* d_part, uint32_t* d_flags) {
+    return E::miller_pairs(c, st, (const uint8_t*)d_g1s, (const uint8_t*)d_g2s, n, d_part, d_flags);
+  });
+}
+
+template <class C>
+int pair_batch_dev_t(const void* d_g1s, const void* d_g2s, size_t n, void* d_gt_out, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const hipStream_t st = k.st;
+  return gt_values_run<C>(c, st, n, nullptr, {(uint8_t*)d_gt_out, nullptr, true}, [&](uint8_t* d_part, uint32_t* d_flags) {
+    return Engine<C>::miller_pairs(c, st, (const uint8_t*)d_g1s, (const uint8_t*)d_g2s, n, d_part, d_flags);
+  });
+}
+
 // ---- the combined check for Boneh-Boyen signatures: one random linear combination per group (bgls_bb_verify_batch_combined) ----
 // n Boneh-Boyen items under ONE check per group of consecutive items: with rho_b the coefficients of bgls_rlc_coefficients and
 // s_g = sum of rho_b over group g as a plain integer, verdict g = [ prod_b e(rho_b sigma_b, Q_b) * e(-s_g g1, g2) == 1 ] over the items b of

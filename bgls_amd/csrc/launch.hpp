@@ -106,6 +106,11 @@ void bb_keys(hipStream_t st, const uint8_t* keys, const uint8_t* rs, const uint8
 template <class C> void bb_w_bytes(hipStream_t st, const Fp2<C>* w, size_t n, uint8_t* out);
 template <class C> void bb_verdicts(hipStream_t st, const uint8_t* gt, size_t n, uint32_t* verdicts);
 
+// ---- k_pairbatch.hip: batched pairings and final exponentiations (bgls_pair_batch, bgls_final_exp_batch).  g1_inf_fill: n G1 points at
+// infinity.  is_one_bytes: out[b] = (words[b] != 0) for b < n.
+template <class C> void g1_inf_fill(hipStream_t st, Aff<F1<C>>* out, size_t n);
+void is_one_bytes(hipStream_t st, const uint32_t* words, size_t n, uint8_t* out);
+
 // ---- k_bbrlc.hip: the coefficients of the combined Boneh-Boyen check (bgls_bb_verify_batch_combined; body: bb_rlc.hpp).  bb_rlc_odd: the
 // lowest bit of each of the n 16-byte coefficients set in place.  bb_rlc_sums: out + 32 g <- the sum of the coefficients group_off[g] ..
 // group_off[g + 1] (device offsets) as a 32-byte big-endian magnitude, one wave per group; r16 is 16-byte aligned.

@@ -16,6 +16,10 @@ template <class C> size_t sum_tree_store_bytes(size_t cnt);
 // one block per instance of a batch: partials + b GTB -> gt_out + b GTB (nullable), verdicts[b] = (result == 1 && inst_flags[b] == 0)
 template <class C>
 void finalx_batch(hipStream_t st, const uint8_t* partials, size_t n_inst, uint8_t* gt_out, uint32_t* verdicts, const uint32_t* inst_flags, uint32_t* flags);
+// ---- k_finalxt.hip: the same n final exponentiations in the throughput form (finalxt.hpp: ten items per wave, no block barrier); same
+// arguments and results as finalx_batch, byte for byte
+template <class C>
+void finalxt_batch(hipStream_t st, const uint8_t* partials, size_t n_inst, uint8_t* gt_out, uint32_t* verdicts, const uint32_t* inst_flags, uint32_t* flags);
 template <class C> void finalx_res(hipStream_t st, const uint8_t* partials, size_t count, int do_final_exp, uint8_t* gt_out, uint32_t* res3, const uint32_t* flags_in);
 
 // ---- k_g1x.hip: scalar multiplications on G1, one point per lane on the carry-free limbs (rx_jac1.hpp)

@@ -251,6 +251,33 @@ class CurveSystem:
     def Pair(self, p1, p2):
         return self.PairingProduct([p1], [p2])
 
+    def PairBatch(self, pts1, pts2):
+        """len(pts1) independent Pair calls in one bgls_pair_batch call: a list with Pair's PointT per item, None where Pair itself
+        answers (nil, false).  An item that is not a G1 / G2 Point of this curve, or a call that fails as a whole (an encoding error
+        somewhere in the batch), is settled item by item with Pair."""
+        if len(pts1) != len(pts2):
+            raise ValueError("pts1 and pts2 differ in length")
+        n = len(pts1)
+        if n == 0:
+            return []
+        gtb = 12 * self.fp_bytes
+        out = [None] * n
+        batch = [i for i, (a, b) in enumerate(zip(pts1, pts2))
+                 if isinstance(a, Point) and isinstance(b, Point) and a.curve is self and b.curve is self and a.group == G1 and b.group == G2]
+        if batch:
+            o = _lib.out(len(batch) * gtb)
+            rc = _lib.load().bgls_pair_batch(self.id, _lib.buf(b"".join(pts1[i].raw for i in batch)), _lib.buf(b"".join(pts2[i].raw for i in batch)),
+                                             len(batch), o)
+            if rc == 0:
+                raw = bytes(o)
+                for k, i in enumerate(batch):
+                    out[i] = PointT(self, raw[k * gtb:(k + 1) * gtb])
+            else:
+                batch = []
+        for i in set(range(n)) - set(batch):
+            out[i] = self.Pair(pts1[i], pts2[i])[0]
+        return out
+
     def PairingProduct(self, pts1, pts2):
         """One C call for the whole slice (replaces concurrentPairingProduct, curve.go:125-170)."""
         if len(pts1) != len(pts2):

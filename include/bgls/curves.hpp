@@ -123,6 +123,33 @@ struct CurveSystem {
     if (bgls_pairing_product(id, g1.data(), g2.data(), p1.size(), o.data()) != 0) return {PointT{}, false};
     return {PointT{this, o}, true};
   }
+  // p1.size() independent Pair calls in ONE bgls_pair_batch call: Pair's PointT per item, an invalid PointT where Pair itself answers
+  // (nil, false); empty when the lengths differ.  An item that is not a G1 / G2 Point of this curve, or a call that fails as a whole (an
+  // encoding error somewhere in the batch), is settled item by item with Pair.
+  std::vector<PointT> PairBatch(const std::vector<Point>& p1, const std::vector<Point>& p2) const {
+    std::vector<PointT> out;
+    if (p1.size() != p2.size()) return out;
+    const size_t n = p1.size(), gtb = bgls_gt_size(id);
+    out.resize(n);
+    std::vector<size_t> batch;
+    std::vector<bool> done(n, false);
+    Bytes g1, g2;
+    for (size_t i = 0; i < n; ++i) {
+      if (p1[i].curve != this || p2[i].curve != this || p1[i].group != BGLS_G1 || p2[i].group != BGLS_G2) continue;
+      batch.push_back(i);
+      g1.insert(g1.end(), p1[i].raw.begin(), p1[i].raw.end());
+      g2.insert(g2.end(), p2[i].raw.begin(), p2[i].raw.end());
+    }
+    Bytes o(batch.size() * gtb);
+    if (!batch.empty() && bgls_pair_batch(id, g1.data(), g2.data(), batch.size(), o.data()) == 0)
+      for (size_t k = 0; k < batch.size(); ++k) {
+        out[batch[k]] = PointT{this, Bytes(o.begin() + k * gtb, o.begin() + (k + 1) * gtb)};
+        done[batch[k]] = true;
+      }
+    for (size_t i = 0; i < n; ++i)
+      if (!done[i]) out[i] = Pair(p1[i], p2[i]).first;
+    return out;
+  }
 };
 
 inline const CurveSystem* Altbn128() {

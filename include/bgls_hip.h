@@ -369,6 +369,20 @@ int bgls_check_points(int curve, int group, const uint8_t* pts, size_t n, uint8_
 int bgls_generator(int curve, int group, uint8_t* out);
 /* CurveSystem.Pair (curves/altbn128.go:130-141, curves/bls12_381.go:228-236) */
 int bgls_pair(int curve, const uint8_t* g1, const uint8_t* g2, uint8_t* gt_out);
+/* n independent CurveSystem.Pair calls in one set of launches: gt_out[b] = e(g1s[b], g2s[b]), n GT elements, byte-equal to bgls_pair on
+ * the same pair for every pair of on-curve points, inside the order-r subgroups or not.  A pair with a point at infinity yields GT one.
+ * A non-canonical or off-curve point ANYWHERE fails the whole call with BGLS_ERR_ENCODING and leaves gt_out as the caller passed it.
+ * n == 0 returns 0 without touching a pointer; NULL arrays with n > 0 and n at or above 2^30 are BGLS_ERR_ARG, checked before any device
+ * work; BGLS_ERR_NO_DEVICE without a device (no CPU fallback).  Returns 0 or < 0. */
+int bgls_pair_batch(int curve, const uint8_t* g1s, const uint8_t* g2s, size_t n, uint8_t* gt_out);
+/* n independent final exponentiations in one launch: gt_out[b] = gt_in[b]^((p^12 - 1) / r), is_one[b] = (gt_out[b] == 1) as 1 / 0.
+ * gt_in: n GT-size wire values as bgls_miller_product_dev writes partials; any canonical Fp12 value is a legal input (0 gives 0, an
+ * element of Fp6* gives one).  gt_out and is_one are nullable, not both.  A non-canonical coefficient (>= p) ANYWHERE fails the whole
+ * call with BGLS_ERR_ENCODING and leaves the outputs as the caller passed them.  n == 0 returns 0 without touching a pointer; a NULL
+ * gt_in with n > 0, both outputs NULL and n at or above 2^30 are BGLS_ERR_ARG, checked before any device work; BGLS_ERR_NO_DEVICE
+ * without a device.  The batched finish of a caller who shards several verifications: one partial per verification in, one verdict
+ * each out.  Returns 0 or < 0. */
+int bgls_final_exp_batch(int curve, const uint8_t* gt_in, size_t n, uint8_t* gt_out, uint8_t* is_one);
 /* PointT.Add = Fp12 multiplication (curves/altbn128.go:264-271, curves/bls12_381.go:160-168) */
 int bgls_gt_mul(int curve, const uint8_t* a, const uint8_t* b, uint8_t* out);
 /* PointT.Mul (curves/altbn128.go:273-281, curves/bls12_381.go:170-173): gt^k, k a 32-byte big-endian magnitude,
@@ -504,6 +518,11 @@ int bgls_ams_verify_batch_dev(int curve, const void* d_apks, const void* d_agg_k
  * (NULL: the context's stream) before it returns. */
 int bgls_bb_verify_batch_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms,
                              size_t n, uint8_t* verdicts, uint8_t* gt_out, void* stream);
+/* bgls_pair_batch and bgls_final_exp_batch with inputs AND outputs on the device (same layouts; d_is_one: n bytes).  Same semantics and
+ * return value, except that after a failed call the device outputs are undefined; both synchronise `stream` (NULL: the context's
+ * stream) before they return. */
+int bgls_pair_batch_dev(int curve, const void* d_g1s, const void* d_g2s, size_t n, void* d_gt_out, void* stream);
+int bgls_final_exp_batch_dev(int curve, const void* d_gt_in, size_t n, void* d_gt_out, void* d_is_one, void* stream);
 /* bgls_bb_verify_batch_combined with its items on the device (same layouts), then the HOST words group_off, n_groups and seed (they plan
  * the launches).  Same contract and return value; synchronises `stream` (NULL: the context's stream) before it returns. */
 int bgls_bb_verify_batch_combined_dev(int curve, const void* d_sigmas, const void* d_rs, const void* d_keys, const void* d_ms, size_t n,

@@ -411,6 +411,121 @@ def main():
         f.write(t2)
     print("wrote", os.path.normpath(out2), len(t2), "bytes")
 
+    # ---- the throughput final exponentiation (finalxt.hpp, k_finalxt.hip): the whole exponentiation f -> f^((p^12 - 1) / r) as ONE
+    # straight-line program over a small file of register-resident temporaries, run by a single loop on the device (one site of
+    # the six-lane product in the code).  A word is op | dst << 4 | a << 8 | b << 12:
+    #   0 MUL   T[dst] = T[a] T[b]                      (the cross-lane product)
+    #   1 CONJ  T[dst] = T[a]^(p^6)                     (lane-local)
+    #   2 FROB  T[dst] = T[a]^(p^b), b = 1 .. 3         (lane-local)
+    #   3 INVD  T[dst] = 1 / (coefficient 0 of T[a]) in Fp2, the same value on every lane of the group
+    #   4 SCALE T[dst] = T[a] times the Fp2 value T[b], coefficient by coefficient (lane-local)
+    # The chains are those of finalx.hpp fx_final_exp (easy part through the norm chain of fx_inv, then the y0 .. y6 chain on alt-bn128
+    # and c (x + p)(x^2 + p^2 - 1) + 1 on BLS12-381) with left-to-right powers.  Checked here: every value of the program is f to a
+    # known exponent modulo p^12 - 1, and the last one is (p^12 - 1) / r; the temporaries are allocated by last use into the smallest
+    # file that holds them, at most NT_MAX.
+    MUL, CONJ, FROB, INVD, SCALE = range(5)
+    NT_MAX = 8
+
+    def fxt_program(cname, p, r, hard):
+        order = p ** 12 - 1
+        ops, exps = [], [1]                                # SSA: value 0 is the input; ops[k] defines value k + 1
+
+        def op(code, a, b, e):
+            ops.append((code, a, b))
+            exps.append(None if e is None else e % order)
+            return len(exps) - 1
+        mul = lambda a, b: op(MUL, a, b, exps[a] + exps[b])
+        conj = lambda a: op(CONJ, a, 0, exps[a] * p ** 6)
+        frob = lambda a, k: op(FROB, a, k, exps[a] * p ** k)
+
+        def inv(a):                                        # fx_inv: N = a conj(a) in Fp6, d = N N^(p^2) N^(p^4) in Fp2, a^-1 = conj(a) N^(p^2) N^(p^4) / d
+            ca = conj(a)
+            n = mul(a, ca)
+            n2 = frob(n, 2)
+            n4 = frob(n2, 2)
+            m = mul(n2, n4)
+            d = mul(n, m)
+            assert exps[d] * (p ** 2 - 1) % order == 0     # d lies in Fp2: only its coefficient 0 is read
+            di = op(INVD, d, 0, None)
+            ni = op(SCALE, m, di, exps[m] - exps[d])
+            assert (exps[ni] + exps[n]) % order == 0
+            return mul(ca, ni)
+
+        def power(a, e):                                   # left to right
+            acc = a
+            for bit in bin(e)[3:]:
+                acc = mul(acc, acc)
+                if bit == "1":
+                    acc = mul(acc, a)
+            return acc
+        f = 0
+        t = mul(conj(f), inv(f))                           # easy part: (p^6 - 1)(p^2 + 1)
+        f = mul(frob(t, 2), t)
+        assert exps[f] == (p ** 6 - 1) * (p ** 2 + 1) % order
+        f = hard(f, mul, conj, frob, power)
+        assert exps[f] == order // r and order % r == 0, cname
+        # registers by last use; a destination may be one of its own operands
+        last = {}
+        for k, (code, a, b) in enumerate(ops):
+            last[a] = k
+            if code in (MUL, SCALE):
+                last[b] = k
+        def allocate(nt):
+            reg, free, words = {0: 0}, list(range(nt - 1, 0, -1)), []
+            for k, (code, a, b) in enumerate(ops):
+                ra, rb = reg[a], (reg[b] if code in (MUL, SCALE) else b)
+                for v in {a} | ({b} if code in (MUL, SCALE) else set()):
+                    if last[v] == k:
+                        free.append(reg.pop(v))
+                if not free:
+                    return None
+                reg[k + 1] = free.pop()
+                words.append(code | reg[k + 1] << 4 | ra << 8 | rb << 12)
+            return words, reg[f]
+        NT = next(nt for nt in range(2, 17) if allocate(nt))          # the smallest file the program fits: NT (2 NL) registers per lane
+        assert NT <= NT_MAX, (cname, NT)
+        words, out_reg = allocate(NT)
+        nmul = sum(1 for c, _, _ in ops if c == MUL)
+        o = "template <>\nstruct FxtK<%s> {\n" % cname
+        o += "  static constexpr int NT = %d;\n  static constexpr int PROG_LEN = %d;\n  static constexpr int PROG_MULS = %d;\n" % (NT, len(words), nmul)
+        o += "  static constexpr int OUT_REG = %d;\n" % out_reg
+        o += arr("PROG", words)
+        return o + "};\n"
+
+    def hard_bn(f, mul, conj, frob, power):
+        a = power(f, u)
+        b = power(a, u)
+        c = power(b, u)
+        y0 = mul(mul(frob(f, 1), frob(f, 2)), frob(f, 3))
+        y4 = conj(mul(a, frob(b, 1)))
+        y6 = conj(mul(c, frob(c, 1)))
+        y1, y2, y3, y5 = conj(f), frob(b, 2), conj(frob(a, 1)), conj(b)
+        t0 = mul(mul(mul(y6, y6), y4), y5)
+        t1 = mul(mul(y3, y5), t0)
+        t0 = mul(t0, y2)
+        t1 = mul(t1, t1)
+        t1 = mul(t1, t0)
+        t1 = mul(t1, t1)
+        t0 = mul(t1, y1)
+        t1 = mul(t1, y0)
+        return mul(t1, mul(t0, t0))
+
+    def hard_bls(f, mul, conj, frob, power):
+        a = power(f, (x - 1) ** 2 // 3)                     # (p^4 - p^2 + 1) / r = c (x + p)(x^2 + p^2 - 1) + 1, c = (x - 1)^2 / 3, x < 0
+        b = mul(conj(power(a, -x)), frob(a, 1))
+        d = conj(power(conj(power(b, -x)), -x))
+        d = mul(mul(d, frob(b, 2)), conj(b))
+        return mul(d, f)
+    t3 = "// GENERATED by tools/gen_constants.py -- do not edit.\n#pragma once\n#include \"constants_gen.hpp\"\n\nnamespace bgls {\n\n"
+    t3 += "enum { FXT_MUL = 0, FXT_CONJ = 1, FXT_FROB = 2, FXT_INVD = 3, FXT_SCALE = 4 };\n"
+    t3 += "template <class C>\nstruct FxtK;\n"
+    t3 += fxt_program("BN254", p_bn, r_bn, hard_bn) + fxt_program("BLS381", p_bls, r_bls, hard_bls)
+    t3 += "}  // namespace bgls\n"
+    out3 = os.path.join(os.path.dirname(OUT), "constants_fxt_gen.hpp")
+    with open(out3, "w") as f:
+        f.write(t3)
+    print("wrote", os.path.normpath(out3), len(t3), "bytes")
+
 
 if __name__ == "__main__":
     main()
