@@ -88,6 +88,10 @@ SIGNATURES = {
     "bgls_miller_product_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, sz, sz, ci, vp, vp, vp]),
     "bgls_verify_multi_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, vp]),
     "bgls_verify_multi_keys_submit_dev": (ci, [ctypes.c_uint64, vp, vp, sz, vp]),
+    "bgls_aggregate_subsets_h": (ci, [ctypes.c_uint64, u8p, sz, sz, u8p]),
+    "bgls_verify_multi_subsets_h": (ci, [ctypes.c_uint64, u8p, u8p, sz, sz, u8p, u64p, u8p, u8p, u8p]),
+    "bgls_verify_multi_subsets_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, u8p, vp]),
+    "bgls_set_subset_complement": (ci, [ci]),
     "bgls_rccl_available": (ci, []),
     "bgls_verify_aggregate_h_gt": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, ci, u8p]),
     "bgls_generator": (ci, [ci, ci, u8p]),

@@ -210,6 +210,83 @@ def KoskVerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
     return _verify_multi_sets(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
 
 
+def _subset_rows(keyset, subsets):
+    """The bitmap rows of `subsets` over a KeySet, ceil(n / 8) bytes each: a subset is a list of key indices (each below len(keyset), a
+    repeated index counts once) or a bytes bitmap (key i selected iff (row[i >> 3] >> (i & 7)) & 1, at most ceil(n / 8) bytes)."""
+    n = len(keyset)
+    stride = (n + 7) // 8
+    rows = bytearray(stride * len(subsets))
+    for b, sub in enumerate(subsets):
+        if isinstance(sub, (bytes, bytearray, memoryview)):
+            sub = bytes(sub)
+            if len(sub) > stride:
+                raise ValueError("subset %d: a bitmap of %d bytes over %d keys" % (b, len(sub), n))
+            rows[b * stride:b * stride + len(sub)] = sub
+        else:
+            for i in sub:
+                if not 0 <= i < n:
+                    raise ValueError("subset %d: key index %d outside the key set" % (b, i))
+                rows[b * stride + (i >> 3)] |= 1 << (i & 7)
+    return bytes(rows), stride
+
+
+def AggregateKeysBySubset(keyset, subsets):
+    """AggregateKeys (bgls/bgls.go:129-131) over len(subsets) sub-slices of a resident KeySet in one bgls_aggregate_subsets_h call: a list
+    of G2 Points.  Nothing of a key travels: a subset is an index list or a bytes bitmap over the registered keys."""
+    if not isinstance(keyset, KeySet):
+        raise TypeError("AggregateKeysBySubset takes a KeySet")
+    if not subsets:
+        return []
+    curve = keyset.curve
+    rows, stride = _subset_rows(keyset, subsets)
+    out = (ctypes.c_uint8 * (len(subsets) * 4 * curve.fp_bytes))()
+    rc = _lib.load().bgls_aggregate_subsets_h(keyset.handle, _lib.buf(rows), stride, len(subsets), out)
+    if rc != 0:
+        raise ValueError("bgls_aggregate_subsets_h: %d %s" % (rc, _lib.last_error()))
+    raw = bytes(out)
+    return [Point(curve, G2, raw[b * 4 * curve.fp_bytes:(b + 1) * 4 * curve.fp_bytes]) for b in range(len(subsets))]
+
+
+def VerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, msgs):
+    """len(aggsigs) independent verifyMultiSignature calls (bgls/bgls.go:89-92) whose signers are sub-slices of ONE resident KeySet -- a
+    MultiSig{keys, sig, msg} over registered keys is one row -- in one bgls_verify_multi_subsets_h call: a list of bools, one per set.  A
+    nil or foreign signature is False without a call; a call that fails as a whole (an off-curve signature, an exhausted hash) is settled
+    set by set, so that the list equals the single calls' results."""
+    if not isinstance(keyset, KeySet):
+        raise TypeError("VerifyMultiSignaturesBySubset takes a KeySet")
+    if not (len(aggsigs) == len(subsets) == len(msgs)):
+        raise ValueError("aggsigs, subsets and msgs differ in length")
+    out = [False] * len(aggsigs)
+    if keyset.curve is not curve:
+        return out
+    batch = [b for b, s in enumerate(aggsigs) if isinstance(s, Point) and s.curve is curve and s.group == G1]
+    if not batch:
+        return out
+    rows, stride = _subset_rows(keyset, [subsets[b] for b in batch])
+    ms = [bytes(msgs[b]) for b in batch]
+
+    def call(idx):
+        verdicts = (ctypes.c_uint8 * len(idx))()
+        rc = _lib.load().bgls_verify_multi_subsets_h(keyset.handle, _lib.buf(b"".join(aggsigs[batch[i]].raw for i in idx)),
+                                                     _lib.buf(b"".join(rows[i * stride:(i + 1) * stride] for i in idx)), stride, len(idx),
+                                                     _lib.buf(b"".join(ms[i] for i in idx)), _offsets([ms[i] for i in idx]), verdicts, None, None)
+        return rc, verdicts
+
+    rc, verdicts = call(list(range(len(batch))))
+    for i, b in enumerate(batch):
+        if rc >= 0:
+            out[b] = verdicts[i] == 1
+        else:
+            rc1, v1 = call([i])
+            out[b] = rc1 >= 0 and v1[0] == 1
+    return out
+
+
+def KoskVerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, msgs):
+    """The same for KoskVerifyMultiSignature (bgls/blsKosk.go:117-120): 0x01 prepended to every message."""
+    return VerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, [b"\x01" + bytes(m) for m in msgs])
+
+
 def _group_offsets(n, group):
     """n_groups + 1 offsets of consecutive chunks of `group` sets (None: one group)"""
     if group is None:

@@ -529,6 +529,64 @@ int bgls_verify_multi_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* m
   DISPATCH(ks->curve, verify_multi_h_t<CV>(*ks, sig, msg, msg_len));
 } BGLS_ABI_GUARD
 
+// Multi-signatures by signer bitmap against a one-device key set.  Order of the refusals: what the arguments alone decide (NULL arrays,
+// alignment), then the machine (no device: a handle can only come from an upload to one), then what the handle decides -- all before any
+// device work.  n_sets == 0 returns 0 first of all.
+static int subsets_no_device() {
+  int cnt = 0;
+  const hipError_t e0 = hipGetDeviceCount(&cnt);
+  return (e0 != hipSuccess || cnt <= 0) ? fail(BGLS_ERR_NO_DEVICE, "no HIP device available", e0) : 0;
+}
+static int subsets_keyset(bgls_keys_t handle, size_t stride, size_t n_sets, std::shared_ptr<KeySet>* ks) {
+  int rc;
+  if ((rc = subsets_no_device())) return rc;
+  if (!(*ks = keyset(handle))) return fail(BGLS_ERR_ARG, "unknown key-set handle");
+  DISPATCH((*ks)->curve, subsets_args_ok<CV>(**ks, stride, n_sets));
+}
+
+int bgls_aggregate_subsets_h(bgls_keys_t handle, const uint8_t* bitmaps, size_t stride, size_t n_sets, uint8_t* out) try {
+  if (n_sets == 0) return 0;
+  if (n_sets >= MAX_BATCH) return too_large();
+  if (!bitmaps || !out) return fail(BGLS_ERR_ARG, "NULL argument");
+  std::shared_ptr<KeySet> ks;
+  int rc;
+  if ((rc = subsets_keyset(handle, stride, n_sets, &ks))) return rc;
+  if (!subset_rows_clean(bitmaps, stride, n_sets, ks->n)) return fail(BGLS_ERR_ARG, "a signer bitmap has a bit at a position beyond the key set");
+  DISPATCH(ks->curve, aggregate_subsets_t<CV>(*ks, bitmaps, stride, n_sets, out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_multi_subsets_h(bgls_keys_t handle, const uint8_t* sigs, const uint8_t* bitmaps, size_t stride, size_t n_sets, const uint8_t* msg_blob,
+                                const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) try {
+  if (n_sets == 0) return 0;
+  if (n_sets >= MAX_BATCH) return too_large();
+  if (!sigs || !bitmaps || !msg_off || !verdicts) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n_sets, 0))) return rc;
+  if (msg_off[n_sets] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  std::shared_ptr<KeySet> ks;
+  if ((rc = subsets_keyset(handle, stride, n_sets, &ks))) return rc;
+  if (!subset_rows_clean(bitmaps, stride, n_sets, ks->n)) return fail(BGLS_ERR_ARG, "a signer bitmap has a bit at a position beyond the key set");
+  DISPATCH(ks->curve, verify_multi_subsets_t<CV>(*ks, sigs, bitmaps, stride, n_sets, msg_blob, msg_off, verdicts, apk_out, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_multi_subsets_keys_dev(bgls_keys_t handle, const void* d_sigs, const void* d_bitmaps, size_t stride, size_t n_sets, const void* d_msgs,
+                                       size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream) try {
+  if (n_sets == 0) return 0;
+  if (n_sets >= MAX_BATCH) return too_large();
+  if (!d_sigs || !d_bitmaps || !verdicts || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if ((stride & 3) || ((uintptr_t)d_bitmaps & 3)) return fail(BGLS_ERR_ARG, "device bitmaps: the stride and the pointer must be multiples of 4 bytes");
+  std::shared_ptr<KeySet> ks;
+  int rc;
+  if ((rc = subsets_keyset(handle, stride, n_sets, &ks))) return rc;
+  DISPATCH(ks->curve, verify_multi_subsets_dev_t<CV>(*ks, d_sigs, d_bitmaps, stride, n_sets, d_msgs, msg_len, msg_stride, verdicts, apk_out, gt_out, stream));
+} BGLS_ABI_GUARD
+
+int bgls_set_subset_complement(int mode) try {
+  if (mode < 0 || mode > 2) return fail(BGLS_ERR_ARG, "mode must be 0 (per set), 1 (never) or 2 (always)");
+  g_subset_complement.store(mode);
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_verify_aggregate_multi(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                                 size_t n, int allow_duplicates, const int* devices, int n_devices) try {
   if (n >= MAX_BATCH) return too_large();

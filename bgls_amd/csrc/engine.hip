@@ -39,6 +39,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 #include "miller_kernels.hpp"
 #include "launch.hpp"
 #include "launch_tail.hpp"
+#include "sumsel.hpp"
 #include "../../include/bgls_hip.h"
 
 using namespace bgls;

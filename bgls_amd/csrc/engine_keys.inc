@@ -53,12 +53,14 @@ struct KeySet {
   std::vector<ncclComm_t> comms;     // one per shard when the RCCL exchange is usable, else empty
   std::mutex mu;                     // one verification at a time per key set (the shards' buffers are part of it)
   int base_ctx = 0;                  // context of shard 0 in the verification in flight (the caller's bgls_select_context)
+  void* d_total = nullptr;           // one-shard sets: the sum of ALL keys as one sum-ready record (keyset_total: made by the first subset call)
   ~KeySet() {
     for (auto cm : comms) if (cm) (void)rccl().CommDestroy(cm);
     for (auto& sh : shards) {
       if (hipSetDevice(sh.device) != hipSuccess) continue;
       for (void* q : {sh.d_wire, sh.d_mont, sh.d_sumr, sh.d_rec, sh.d_all, sh.d_prep, sh.d_kinf}) if (q) (void)hipFree(q);
     }
+    if (d_total && !shards.empty() && hipSetDevice(shards[0].device) == hipSuccess) (void)hipFree(d_total);
   }
 };
 std::mutex g_keys_mu;
@@ -411,6 +413,169 @@ int verify_multi_h_t(KeySet& ks, const uint8_t* sig, const uint8_t* msg, size_t 
     return verify_multi_dev_t<C>(c, st, (const uint8_t*)d_sig, (const uint8_t*)d_apk, 1, (const uint8_t*)d_msg, msg_len);
   }();
   return rc;
+}
+
+// ---- multi-signatures by signer bitmap against a one-shard key set (bgls_verify_multi_subsets_h / _keys_dev, bgls_aggregate_subsets_h) ----
+// bgls_set_subset_complement: 0 = per set (the shorter side of the row), 1 = never, 2 = always.  The sums do not depend on it.
+std::atomic<int> g_subset_complement{0};
+
+// What a subset call must find before any device work: a one-shard set, the lane-pair key sum (the only reader of sum-ready records), a
+// row stride that covers the set, and a batch within the bounds of one main-pass launch (those of Engine::sum_sets).
+template <class C>
+int subsets_args_ok(const KeySet& ks, size_t stride, size_t n_sets) {
+  if (ks.shards.size() != 1) return fail(BGLS_ERR_ARG, "subset entry point: the key set must live on one device");
+  if (!sum_pairs()) return fail(BGLS_ERR_ARG, "subset entry point: needs the lane-pair key sum (BGLS_LEGACY bit 8 is set)");
+  if (stride < (ks.n + 7) / 8) return fail(BGLS_ERR_ARG, "bitmap stride is shorter than ceil(n / 8) bytes");
+  if (n_sets >= MAX_BATCH) return too_large();
+  const size_t blocks = n_sets * (sumsel_pairs_per_set(ks.n, n_sets) / 32);
+  if (blocks > ((size_t)1 << 30) || (blocks + 1) * kl::jac_bytes<C>(BGLS_G2) > ((size_t)8 << 30))
+    return fail(BGLS_ERR_ARG, "too many key sets for one call (cut the batch: at most 2^30 blocks / 8 GiB of partial sums)");
+  return 0;
+}
+
+// a host row has no bit at a position >= n, anywhere in its `stride` bytes
+bool subset_rows_clean(const uint8_t* bitmaps, size_t stride, size_t n_sets, size_t n) {
+  const size_t full = n / 8;
+  for (size_t b = 0; b < n_sets; ++b) {
+    const uint8_t* row = bitmaps + b * stride;
+    if (full < stride && (n & 7) && (row[full] >> (n & 7))) return false;
+    for (size_t i = (n + 7) / 8; i < stride; ++i)
+      if (row[i]) return false;
+  }
+  return true;
+}
+
+// The whole-set sum of a one-shard key set as ONE sum-ready record: Engine::sum_points over the resident records, the wire bytes parsed and
+// converted like a key at upload.  Made once, by the first subset call, under the set's mutex; it belongs to the key set (freed with it,
+// not a workspace).  Runs on the calling thread's context of the set's device.
+template <class C>
+int keyset_total(KeySet& ks) {
+  typedef Engine<C> E;
+  std::lock_guard<std::mutex> lk_set(ks.mu);
+  if (ks.d_total) return 0;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  const KeyShard& sh = ks.shards[0];
+  const size_t rec = (kl::g2_sumready_bytes<C>() + 15) & ~(size_t)15, mont = (kl::g2_parsed_bytes<C>() + 15) & ~(size_t)15;
+  void *buf = nullptr, *d_flags;
+  int rc;
+  if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
+  HIPCHK(hipMalloc(&buf, rec + mont + E::G2B));
+  uint8_t* d_rec = (uint8_t*)buf;
+  uint8_t* d_mont = d_rec + rec;
+  uint8_t* d_wire = d_mont + mont;
+  rc = [&]() -> int {
+    int r;
+    HIPCHK(hipMemsetAsync(d_flags, 0, 4, k.st));
+    if ((r = E::sum_points(c, k.st, BGLS_G2, (const uint8_t*)sh.d_sumr, ks.n, d_wire, (uint32_t*)d_flags, 2))) return r;
+    kl::g2_parse<C>(k.st, d_wire, 1, 0, d_mont, (uint32_t*)d_flags);
+    kl::g2_sumready<C>(k.st, d_mont, 1, d_rec);
+    HIPCHK(hipGetLastError());
+    return read_flags(c, k.st, d_flags, true);
+  }();
+  if (rc) {
+    (void)hipStreamSynchronize(k.st);
+    (void)hipFree(buf);
+    return rc;
+  }
+  ks.d_total = buf;
+  return 0;
+}
+
+// The n_sets key sums selected by the rows at d_rows (stride_w 32-bit words each) as wire bytes at d_out: the planning pass (popcount and
+// mode per set in WS_SEG_OFF, FLAG_SUBSET_STRAY in d_flags), k_sumsel_main over the set's sum-ready records, then Engine::sum_sets_tree.
+template <class C>
+int sum_subsets(Ctx& c, hipStream_t st, const KeySet& ks, const uint32_t* d_rows, size_t stride_w, size_t n_sets, uint8_t* d_out, uint32_t* d_flags) {
+  typedef Engine<C> E;
+  if (n_sets == 0) return 0;
+  const size_t P = sumsel_pairs_per_set(ks.n, n_sets), written = n_sets * (P / 32), JB = kl::jac_bytes<C>(BGLS_G2);
+  void *ja, *jb, *plan;
+  int rc;
+  Scope sc(c, st, ST_SUM);
+  if ((rc = c.get(WS_JAC_A, (written + 1) * JB, &ja))) return rc;
+  if ((rc = c.get(WS_JAC_B, (written / 2 + 2) * JB, &jb))) return rc;
+  if ((rc = c.get(WS_SEG_OFF, n_sets * 8, &plan))) return rc;
+  {
+    Scope scm(c, st, ST_SUM_MAIN);
+    kl::sumsel_plan(st, d_rows, stride_w, ks.n, n_sets, g_subset_complement.load(), (uint32_t*)plan, d_flags);
+    kl::sumsel_main<C>(st, (const uint8_t*)ks.shards[0].d_sumr, ks.n, d_rows, stride_w, (const uint32_t*)plan, (const uint8_t*)ks.d_total, n_sets, (unsigned)P, ja);
+  }
+  E::sum_sets_tree(st, BGLS_G2, ja, jb, P / 32, n_sets, d_out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// host rows (stride bytes each, checked) repacked to whole 32-bit words per row and staged in WS_IN_B; packed is the copy's source
+template <class C>
+int upload_subset_rows(Ctx& c, hipStream_t st, const KeySet& ks, const uint8_t* bitmaps, size_t stride, size_t n_sets, std::vector<uint32_t>& packed, void** d_rows,
+                       size_t* stride_w) {
+  const size_t nb = (ks.n + 7) / 8, sw = (ks.n + 31) / 32;
+  packed.assign(n_sets * sw, 0u);
+  for (size_t b = 0; b < n_sets && nb; ++b) memcpy((uint8_t*)packed.data() + b * sw * 4, bitmaps + b * stride, nb);
+  *stride_w = sw;
+  return c.put(st, WS_IN_B, packed.data(), packed.size() * 4, d_rows);
+}
+
+template <class C>
+int aggregate_subsets_t(KeySet& ks, const uint8_t* bitmaps, size_t stride, size_t n_sets, uint8_t* out) {
+  typedef Engine<C> E;
+  int rc;
+  SelectionGuard keep_selection;
+  g_dev = ks.shards[0].device;
+  if ((rc = keyset_total<C>(ks))) return rc;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  void *d_rows, *d_out, *d_flags;
+  size_t sw;
+  std::vector<uint32_t> packed;                           // alive until read_flags has synchronised
+  Drain drain{k.st};
+  if ((rc = c.get(WS_SEG_KEYS, (n_sets + 1) * E::G2B, &d_out))) return rc;
+  if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
+  HIPCHK(hipMemsetAsync(d_flags, 0, 4, k.st));
+  if ((rc = upload_subset_rows<C>(c, k.st, ks, bitmaps, stride, n_sets, packed, &d_rows, &sw))) return rc;
+  if ((rc = sum_subsets<C>(c, k.st, ks, (const uint32_t*)d_rows, sw, n_sets, (uint8_t*)d_out, (uint32_t*)d_flags))) return rc;
+  return read_flags(c, k.st, d_flags, true, out, d_out, n_sets * E::G2B);
+}
+
+template <class C>
+int verify_multi_subsets_t(KeySet& ks, const uint8_t* sigs, const uint8_t* bitmaps, size_t stride, size_t n_sets, const uint8_t* blob, const uint64_t* off,
+                           uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  int rc;
+  SelectionGuard keep_selection;
+  g_dev = ks.shards[0].device;
+  if ((rc = keyset_total<C>(ks))) return rc;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  MsgView mv;
+  void *d_sigs, *d_rows;
+  size_t sw;
+  std::vector<uint32_t> packed;
+  if ((rc = upload_msgs(c, k.st, blob, off, n_sets, &mv))) return rc;
+  if ((rc = c.put(k.st, WS_IN_A, sigs, n_sets * E::G1B, &d_sigs))) return rc;
+  if ((rc = upload_subset_rows<C>(c, k.st, ks, bitmaps, stride, n_sets, packed, &d_rows, &sw))) return rc;
+  HIPCHK(hipStreamSynchronize(k.st));                     // packed may go out of scope on an error path below
+  return verify_sets_run<C>(c, k.st, (const uint8_t*)d_sigs, n_sets, mv, verdicts, apk_out, gt_out, [&](uint8_t* d_apks, uint32_t* d_flags) {
+    return sum_subsets<C>(c, k.st, ks, (const uint32_t*)d_rows, sw, n_sets, d_apks, d_flags);
+  });
+}
+
+template <class C>
+int verify_multi_subsets_dev_t(KeySet& ks, const void* d_sigs, const void* d_bitmaps, size_t stride, size_t n_sets, const void* d_msgs, size_t msg_len,
+                               size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out, void* stream) {
+  int rc;
+  SelectionGuard keep_selection;
+  g_dev = ks.shards[0].device;
+  if ((rc = keyset_total<C>(ks))) return rc;
+  Call k(stream);
+  if (k.rc) return k.rc;
+  const MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_sets_run<C>(k.c, k.st, (const uint8_t*)d_sigs, n_sets, mv, verdicts, apk_out, gt_out, [&](uint8_t* d_apks, uint32_t* d_flags) {
+    return sum_subsets<C>(k.c, k.st, ks, (const uint32_t*)d_bitmaps, stride / 4, n_sets, d_apks, d_flags);
+  });
 }
 
 bool group_ok(int g) { return g == BGLS_G1 || g == BGLS_G2; }

@@ -1,6 +1,7 @@
 // Host side, part 2 of 4 (included by engine.hip): the per-call bodies behind the C ABI -- VerifyAggregateSignature / VerifyMultiSignature
 // and their batch, device-buffer and weighted (multiplicity / HAE) forms, point operations, wire formats, key generation and signing.
 int flags_to_rc(uint32_t f) {
+  if (f & FLAG_SUBSET_STRAY) return fail(BGLS_ERR_ARG, "a signer bitmap has a bit at a position beyond the key set");
   if (f & FLAG_ENC) return fail(BGLS_ERR_ENCODING, "non-canonical coordinate or point not on curve");
   if (f & FLAG_SUBGROUP) return fail(BGLS_ERR_ENCODING, "point outside the order-r subgroup");
   if (f & FLAG_DEGENERATE) return fail(BGLS_ERR_ENCODING, "degenerate point step (small-order key)");

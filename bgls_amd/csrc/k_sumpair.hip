@@ -10,6 +10,7 @@
 #include "coop.hpp"
 #include "rx_jacpair.hpp"
 #include "launch.hpp"
+#include "sumsel.hpp"
 
 namespace bgls {
 
@@ -194,6 +195,122 @@ __global__ void __launch_bounds__(64, 3) k_sumpairseg_main(const uint8_t* pts, c
   if (threadIdx.x < 2) sumpair_store<C>(out + blockIdx.x, acc, odd);      // partials of set b: blocks b * per .. (b + 1) * per - 1
 }
 
+// ---- key sums by signer bitmap over a key set's sum-ready records (bgls_verify_multi_subsets_h, bgls_aggregate_subsets_h) ----
+// Planning pass, one wave per set: the row's popcount over [0, n) and its mode to plan[2 b], plan[2 b + 1] (1 = complement: the block
+// adds the negated keys that are NOT selected, and block 0 of the set the whole-set sum), FLAG_SUBSET_STRAY where the row has a bit at a
+// position >= n (anywhere in its stride_w words).
+__global__ void __launch_bounds__(64) k_sumsel_plan(const uint32_t* rows, size_t stride_w, size_t n, int mode, uint32_t* plan, uint32_t* flags) {
+  const size_t b = blockIdx.x;
+  const unsigned lane = threadIdx.x;
+  const uint32_t* row = rows + b * stride_w;
+  unsigned cnt = 0;
+  bool stray = false;
+  for (size_t w = lane; w < stride_w; w += 64) {
+    uint32_t v = row[w];
+    const size_t base = w * 32;
+    if (base >= n) {
+      stray = stray || v != 0;
+      continue;
+    }
+    const size_t rem = n - base;
+    if (rem < 32) {
+      stray = stray || (v >> rem) != 0;
+      v &= (1u << rem) - 1u;
+    }
+    cnt += __popc(v);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+  if (__ballot(stray) != 0 && lane == 0) atomicOr(flags, FLAG_SUBSET_STRAY);
+  if (lane == 0) {
+    plan[2 * b] = cnt;
+    plan[2 * b + 1] = sumsel_complement(cnt, n, mode) ? 1u : 0u;
+  }
+}
+
+// Main pass.  Block c of the `per` one-wave blocks of set b takes windows c, c + per, ... of 2048 key positions: every lane loads ONE
+// word of the row per window (coalesced; sumsel_word clears what lies beyond n and inverts in complement mode).  The work follows the
+// selected keys, not the set size: eight lanes' words at a time (256 positions) are compacted -- per-lane popcounts, a prefix sum over
+// the eight lanes -- into a ring of key indices in LDS, and whenever 32 entries are pending lane pair p takes entry p of them, fetches
+// the key's sum-ready record and adds it (jacp_madd: every exceptional case of the group law is decided there).  Fewer than 32 pending
+// entries stay in the ring while input is left, so pairs idle only in the last round of a block.  Complement mode: y is negated on the
+// carry-free limbs, and block 0 appends one more entry, TOTAL, for the whole-set sum (one sum-ready record at `total`, not negated).
+// The ring holds at most 31 + 256 entries: 1152 bytes beside the block tree's columns (see DESIGN.md section 5 for the LDS budget).
+constexpr unsigned SUMSEL_RING = 288;
+constexpr uint32_t SUMSEL_TOTAL = 0xFFFFFFFFu;          // key indices are below 2^30
+__device__ __forceinline__ unsigned sumsel_wrap(unsigned x) { return x >= SUMSEL_RING ? x - SUMSEL_RING : x; }      // x < 2 SUMSEL_RING
+
+template <class C>
+__global__ void __launch_bounds__(64, 3) k_sumsel_main(const uint8_t* recs, size_t n, const uint32_t* rows, size_t stride_w, const uint32_t* plan,
+                                                       const uint8_t* total, unsigned per, Jac<F2<C>>* out) {
+  __shared__ uint32_t ring[SUMSEL_RING];
+  const unsigned lane = threadIdx.x, pair = lane >> 1;
+  const bool odd = lane & 1;
+  const size_t b = blockIdx.x / per;
+  const unsigned c = blockIdx.x % per;
+  const bool comp = plan[2 * b + 1] != 0;
+  const uint32_t* row = rows + b * stride_w;
+  const size_t nwin = sumsel_windows(n);
+  JacP<C> acc = jacp_inf<C>();
+  size_t win = sumsel_first_window(c);
+  uint32_t w = 0, wbase = 0;
+  uint64_t nz = 0;
+  unsigned step = 8;                                    // 8: no window loaded
+  unsigned head = 0, pending = 0;
+  bool total_due = comp && c == 0;
+#pragma unroll 1
+  for (;;) {
+#pragma unroll 1
+    while (pending < 32) {
+      if (step == 8) {
+        if (win >= nwin) break;
+        w = sumsel_word(row, n, win, lane, comp);
+        wbase = (uint32_t)(win * SUMSEL_WINDOW + lane * 32);
+        nz = __ballot(w != 0);
+        win += sumsel_window_step(per);
+        step = 0;
+      }
+      const unsigned q = step++;
+      if (((nz >> (8 * q)) & 0xFF) == 0) continue;
+      const bool mine = (lane >> 3) == q;
+      const unsigned cnt = mine ? __popc(w) : 0u;
+      unsigned s = cnt;
+#pragma unroll
+      for (int d = 1; d < 8; d <<= 1) {
+        const unsigned t = __shfl_up(s, d, 8);
+        if ((lane & 7) >= (unsigned)d) s += t;
+      }
+      const unsigned tot = __shfl(s, 8 * q + 7, 64);
+      if (mine) {
+        unsigned at = head + pending + (s - cnt);
+        for (uint32_t v = w; v; v &= v - 1) ring[sumsel_wrap(at++)] = wbase + (uint32_t)(__ffs(v) - 1);
+      }
+      pending += tot;
+    }
+    if (pending < 32 && total_due) {                    // the input is exhausted: the whole-set sum goes last
+      if (lane == 0) ring[sumsel_wrap(head + pending)] = SUMSEL_TOTAL;
+      ++pending;
+      total_due = false;
+    }
+    if (pending == 0) break;
+    wave_sync();
+    const unsigned take = pending < 32 ? pending : 32;
+    if (pair < take) {
+      const uint32_t k = ring[sumsel_wrap(head + pair)];
+      const bool whole = k == SUMSEL_TOTAL;
+      AffP<C> q;
+      (void)sumpair_fetch<C, 2>(q, whole ? total : recs, whole ? 0 : k, odd);
+      if (comp && !whole) q.y = sx_neg<C>(q.y);
+      acc = jacp_madd<C>(acc, q, odd);
+    }
+    wave_sync();                                        // the entries are read before their slots are written again
+    head = sumsel_wrap(head + take);
+    pending -= take;
+  }
+  acc = sumpair_block_tree<C>(acc, odd);
+  if (threadIdx.x < 2) sumpair_store<C>(out + blockIdx.x, acc, odd);      // partials of set b: blocks b * per .. (b + 1) * per - 1
+}
+
 // a key set's sum-ready copy: per key 4 NL dwords = x_re y_re | x_im y_im in the carry-free form (tight limbs, value < 2 p),
 // bit 31 of each half's first dword = point at infinity
 template <class C>
@@ -252,6 +369,18 @@ void sumpairseg_main(hipStream_t st, const uint8_t* pts, const uint64_t* off, si
   typedef typename SumForm<C>::type X;
   k_sumpairseg_main<X><<<(unsigned)(nsets * (P / 32)), 64, 0, st>>>(pts, off, P, (Jac<F2<X>>*)out, flags);
 }
+void sumsel_plan(hipStream_t st, const uint32_t* rows, size_t stride_w, size_t n, size_t nsets, int mode, uint32_t* plan, uint32_t* flags) {
+  k_sumsel_plan<<<(unsigned)nsets, 64, 0, st>>>(rows, stride_w, n, mode, plan, flags);
+}
+// P lane pairs per set (sumsel_pairs_per_set); nsets * P / 32 Jacobian partials are written, set-major
+template <class C>
+void sumsel_main(hipStream_t st, const uint8_t* recs, size_t n, const uint32_t* rows, size_t stride_w, const uint32_t* plan, const uint8_t* total, size_t nsets,
+                 unsigned P, void* out) {
+  typedef typename SumForm<C>::type X;
+  k_sumsel_main<X><<<(unsigned)(nsets * (P / 32)), 64, 0, st>>>(recs, n, rows, stride_w, plan, total, P / 32, (Jac<F2<X>>*)out);
+}
+template void sumsel_main<BN254>(hipStream_t, const uint8_t*, size_t, const uint32_t*, size_t, const uint32_t*, const uint8_t*, size_t, unsigned, void*);
+template void sumsel_main<BLS381>(hipStream_t, const uint8_t*, size_t, const uint32_t*, size_t, const uint32_t*, const uint8_t*, size_t, unsigned, void*);
 template void sumpair_main<BN254>(hipStream_t, int, const uint8_t*, size_t, unsigned, void*, uint32_t*);
 template void sumpair_main<BLS381>(hipStream_t, int, const uint8_t*, size_t, unsigned, void*, uint32_t*);
 template void g2_sumready<BN254>(hipStream_t, const void*, size_t, void*);

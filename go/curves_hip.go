@@ -385,6 +385,92 @@ func (ks *HipKeySet) VerifyMulti(aggsig Point, msg []byte) bool {
 	return ok
 }
 
+// subsetRows turns index lists over the resident keys into bitmap rows (key i of a row: bit i&7 of byte i>>3), stride bytes apart;
+// ok = false for an index outside the set.
+func (ks *HipKeySet) subsetRows(subsets [][]int) (rows []byte, stride int, ok bool) {
+	stride = ks.n/8 + 1
+	rows = make([]byte, stride*len(subsets))
+	for b, sub := range subsets {
+		for _, i := range sub {
+			if i < 0 || i >= ks.n {
+				return nil, 0, false
+			}
+			rows[b*stride+i>>3] |= 1 << uint(i&7)
+		}
+	}
+	return rows, stride, true
+}
+
+// HipVerifyMultiSubsets is len(aggsigs) independent verifyMultiSignature calls (bgls/bgls.go:89-92) whose signers are sub-slices of the
+// resident keys -- a MultiSig{keys, sig, msg} (bgls/blsKosk.go:108-112) over registered keys is one index list -- in ONE
+// bgls_verify_multi_subsets_h call: ok[b] is set b's verdict.  A nil or foreign signature is false without a call; a call that fails
+// as a whole is settled set by set.  For KoskVerifyMultiSignature the caller prepends 0x01 to every message.
+// Like the rest of this file this wrapper is text: it has never been compiled (no Go toolchain where the library is built).
+func (ks *HipKeySet) HipVerifyMultiSubsets(aggsigs []Point, subsets [][]int, msgs [][]byte) []bool {
+	out := make([]bool, len(aggsigs))
+	if len(aggsigs) != len(subsets) || len(aggsigs) != len(msgs) {
+		return out
+	}
+	var batch []int
+	for b, a := range aggsigs {
+		if s, ok := a.(*hipPoint); ok && s.c == ks.c && s.group == C.BGLS_G1 {
+			batch = append(batch, b)
+		}
+	}
+	call := func(idx []int) (C.int, []byte) {
+		subs := make([][]int, len(idx))
+		off := make([]C.uint64_t, len(idx)+1)
+		var sb, blob []byte
+		for i, b := range idx {
+			subs[i] = subsets[b]
+			sb = append(sb, aggsigs[b].(*hipPoint).raw...)
+			off[i] = C.uint64_t(len(blob))
+			blob = append(blob, msgs[b]...)
+		}
+		off[len(idx)] = C.uint64_t(len(blob))
+		rows, stride, ok := ks.subsetRows(subs)
+		if !ok {
+			return -1, nil
+		}
+		verdicts := make([]byte, len(idx))
+		rc := C.bgls_verify_multi_subsets_h(ks.h, p(sb), p(rows), C.size_t(stride), C.size_t(len(idx)), p(append(blob, 0)), &off[0], p(verdicts), nil, nil)
+		return rc, verdicts
+	}
+	if len(batch) == 0 {
+		return out
+	}
+	rc, verdicts := call(batch)
+	for i, b := range batch {
+		if rc >= 0 {
+			out[b] = verdicts[i] == 1
+		} else if rc1, v1 := call([]int{b}); rc1 >= 0 {
+			out[b] = v1[0] == 1
+		}
+	}
+	runtime.KeepAlive(ks)
+	return out
+}
+
+// HipAggregateKeysBySubset is AggregateKeys (bgls/bgls.go:129-131) over every index list in ONE bgls_aggregate_subsets_h call; nil on an
+// index outside the set or a failed call.  Uncompiled text, as above.
+func (ks *HipKeySet) HipAggregateKeysBySubset(subsets [][]int) []Point {
+	rows, stride, ok := ks.subsetRows(subsets)
+	if !ok || len(subsets) == 0 {
+		return nil
+	}
+	pb := int(C.bgls_g2_size(ks.c.id))
+	sums := make([]byte, pb*len(subsets))
+	if C.bgls_aggregate_subsets_h(ks.h, p(rows), C.size_t(stride), C.size_t(len(subsets)), p(sums)) != 0 {
+		return nil
+	}
+	runtime.KeepAlive(ks)
+	out := make([]Point, len(subsets))
+	for b := range subsets {
+		out[b] = &hipPoint{ks.c, C.BGLS_G2, append([]byte(nil), sums[b*pb:(b+1)*pb]...)}
+	}
+	return out
+}
+
 // VerifyAggregateDistinct is bgls.DistinctMsgVerifyAggregateSignature (bgls/blsDistinctMessage.go:45-57) against the resident keys:
 // every GPU of the set puts its keys' wire bytes in front of the messages itself, nothing is prefixed here.
 func (ks *HipKeySet) VerifyAggregateDistinct(aggsig Point, msgs [][]byte) bool {

@@ -120,8 +120,83 @@ class KeySet {
     }
     return bgls_verify_aggregate_distinct_h(h_, aggsig.raw.data(), blob.data(), off.data(), n_, nullptr) == 1;
   }
+  // ---- sub-slices of the resident keys: MultiSig{keys, sig, msg} (bgls/blsKosk.go:108-112) over registered keys is one subset ----
+  // A subset is a list of key indices (each below size(); a repeated index counts once).  One bgls_*_subsets_h call per list of subsets.
+  size_t size() const { return n_; }
+  // AggregateKeys (bgls/bgls.go:129-131) over every subset: one G2 point per subset; empty on an index outside the set or a failed call
+  std::vector<Point> AggregateKeysBySubset(const std::vector<std::vector<size_t>>& subsets) const {
+    std::vector<Point> out;
+    Bytes rows;
+    if (!ok_ || subsets.empty() || !subset_rows(subsets, rows)) return out;
+    const size_t pb = curve_->size(BGLS_G2);
+    Bytes sums(subsets.size() * pb);
+    if (bgls_aggregate_subsets_h(h_, rows.data(), stride(), subsets.size(), sums.data()) != 0) return out;
+    for (size_t b = 0; b < subsets.size(); ++b) out.push_back(Point{curve_, BGLS_G2, Bytes(sums.begin() + b * pb, sums.begin() + (b + 1) * pb)});
+    return out;
+  }
+  // aggsigs.size() independent verifyMultiSignature calls (bgls/bgls.go:89-92), set b signed by subset b: one bool per set.  A nil or foreign
+  // signature is false without a call; a call that fails as a whole (an off-curve signature, an exhausted hash) is settled set by set.
+  std::vector<bool> VerifyMultiSignaturesBySubset(const std::vector<Point>& aggsigs, const std::vector<std::vector<size_t>>& subsets,
+                                                  const std::vector<Bytes>& msgs) const {
+    std::vector<bool> out(aggsigs.size(), false);
+    if (!ok_ || aggsigs.size() != subsets.size() || aggsigs.size() != msgs.size()) return out;
+    std::vector<size_t> batch;
+    for (size_t b = 0; b < aggsigs.size(); ++b)
+      if (aggsigs[b].curve == curve_ && aggsigs[b].group == BGLS_G1) batch.push_back(b);
+    auto call = [&](const std::vector<size_t>& idx, std::vector<uint8_t>& verdicts) {
+      std::vector<std::vector<size_t>> subs;
+      Bytes sb, blob, rows;
+      std::vector<uint64_t> off(idx.size() + 1, 0);
+      for (size_t i = 0; i < idx.size(); ++i) {
+        const size_t b = idx[i];
+        subs.push_back(subsets[b]);
+        sb.insert(sb.end(), aggsigs[b].raw.begin(), aggsigs[b].raw.end());
+        blob.insert(blob.end(), msgs[b].begin(), msgs[b].end());
+        off[i + 1] = blob.size();
+      }
+      if (!subset_rows(subs, rows)) return -1;
+      blob.push_back(0);                                   // never an empty array
+      verdicts.assign(idx.size(), 0);
+      return bgls_verify_multi_subsets_h(h_, sb.data(), rows.data(), stride(), idx.size(), blob.data(), off.data(), verdicts.data(), nullptr, nullptr);
+    };
+    if (batch.empty()) return out;
+    std::vector<uint8_t> verdicts;
+    const int rc = call(batch, verdicts);
+    for (size_t i = 0; i < batch.size(); ++i) {
+      if (rc >= 0) {
+        out[batch[i]] = verdicts[i] == 1;
+      } else {
+        std::vector<uint8_t> v1;
+        out[batch[i]] = call({batch[i]}, v1) >= 0 && v1[0] == 1;
+      }
+    }
+    return out;
+  }
+  // the same for KoskVerifyMultiSignature (bgls/blsKosk.go:117-120): 0x01 prepended to every message
+  std::vector<bool> KoskVerifyMultiSignaturesBySubset(const std::vector<Point>& aggsigs, const std::vector<std::vector<size_t>>& subsets,
+                                                      const std::vector<Bytes>& msgs) const {
+    std::vector<Bytes> ms;
+    for (const Bytes& m : msgs) {
+      Bytes p(1, 1);
+      p.insert(p.end(), m.begin(), m.end());
+      ms.push_back(p);
+    }
+    return VerifyMultiSignaturesBySubset(aggsigs, subsets, ms);
+  }
 
  private:
+  size_t stride() const { return n_ / 8 + 1; }             // at least ceil(n / 8), never 0
+  // bitmap rows of the subsets (key i of a row: bit i & 7 of byte i >> 3); false on an index outside the set
+  bool subset_rows(const std::vector<std::vector<size_t>>& subsets, Bytes& rows) const {
+    rows.assign(subsets.size() * stride(), 0);
+    for (size_t b = 0; b < subsets.size(); ++b)
+      for (size_t i : subsets[b]) {
+        if (i >= n_) return false;
+        rows[b * stride() + (i >> 3)] |= (uint8_t)(1u << (i & 7));
+      }
+    return true;
+  }
+
   const CurveSystem* curve_;
   size_t n_;
   bgls_keys_t h_ = 0;

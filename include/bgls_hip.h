@@ -601,6 +601,34 @@ int bgls_miller_product_keys_dev(bgls_keys_t handle, const void* d_sig, const vo
 /* verifyMultiSignature (bgls/bgls.go:89-92) against a resident key set: per-device partial key sums (projective G2
  * points) are gathered on the first device, added, and the two-pairing check runs there. */
 int bgls_verify_multi_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* msg, size_t msg_len);
+/* Multi-signatures by SIGNER BITMAP against a ONE-device key set: MultiSig{keys, sig, msg} (bgls/blsKosk.go:108-112) whose keys are a
+ * sub-slice of the registered keys.  Set b of n_sets is a bitmap row over the set's n keys, `stride` bytes apart: key i is selected iff
+ * (row[i >> 3] >> (i & 7)) & 1.  Nothing of a key is uploaded, parsed or checked again: the key sums read the resident sum-ready records,
+ * and their work follows the selected keys -- or, where more than half of the set is selected, the absentees, subtracted from the sum of
+ * the whole set (computed once per key set, by the first of these calls).
+ *   bgls_aggregate_subsets_h            out[b] = sum of the keys selected by row b (AggregateKeys over the sub-slice): n_sets G2 points
+ *   bgls_verify_multi_subsets_h         n_sets verifyMultiSignature calls (bgls/bgls.go:89-92): set b = sigs[b], the selected keys, message b
+ *   bgls_verify_multi_subsets_keys_dev  the same with signatures, rows and fixed-stride messages on the device, on the calling thread's
+ *                                       context and the given stream; rows are read as 32-bit words: stride and d_bitmaps multiples of 4
+ * verdicts[b], gt_out[b] and apk_out[b] are byte-equal to what bgls_verify_multi_sets and bgls_aggregate_sets return for the gathered keys
+ * of subset b; gt_out and apk_out may be NULL.  An empty subset sums to infinity, and its set is accepted iff its signature is the point at
+ * infinity, as bgls_verify_multi with n = 0.  Returns the number of accepted sets (aggregate: 0) or, for the whole call, the codes of
+ * bgls_verify_multi_sets: BGLS_ERR_ENCODING for a bad signature, BGLS_ERR_HASH for an exhausted hash.
+ * BGLS_ERR_ARG, before any device work: NULL arrays with n_sets > 0; for the device form a stride or pointer that is not 4-byte aligned;
+ * an unknown handle; a key set on more than one device; stride < ceil(n / 8); a batch beyond the launch bounds of bgls_aggregate_sets (2^30
+ * blocks / 8 GiB of partial sums); the lane-pair key sum switched off (BGLS_LEGACY bit 8); a row with a bit at a position >= n, anywhere in
+ * its stride -- found on the host by the host forms, by the planning pass of the device form, which then fails the whole call with the same
+ * code.  n_sets == 0 returns 0 without touching a pointer.  Without a device: BGLS_ERR_NO_DEVICE (decided after the NULL and alignment
+ * checks and before the handle is looked at: a handle can only come from an upload to a device). */
+int bgls_aggregate_subsets_h(bgls_keys_t handle, const uint8_t* bitmaps, size_t stride, size_t n_sets, uint8_t* out);
+int bgls_verify_multi_subsets_h(bgls_keys_t handle, const uint8_t* sigs, const uint8_t* bitmaps, size_t stride, size_t n_sets,
+                                const uint8_t* msg_blob, const uint64_t* msg_off, uint8_t* verdicts, uint8_t* apk_out, uint8_t* gt_out);
+int bgls_verify_multi_subsets_keys_dev(bgls_keys_t handle, const void* d_sigs, const void* d_bitmaps, size_t stride, size_t n_sets,
+                                       const void* d_msgs, size_t msg_len, size_t msg_stride, uint8_t* verdicts, uint8_t* apk_out,
+                                       uint8_t* gt_out, void* stream);
+/* Which side of a row the subset key sums add: 0 = chosen per set (complement when 2 popcount > n; default), 1 = never the complement,
+ * 2 = always.  Process-wide; results do not depend on it (A/B measurements and tests). */
+int bgls_set_subset_complement(int mode);
 /* Contexts: a key-set verification runs shard s on context (selected + s) mod 16 of the shard's device, `selected` being the
  * calling thread's bgls_select_context (default 0); the final product / exponentiation runs on shard 0's context. */
 /* The same two calls with host keys, for callers without a resident set: upload (with BGLS_KEYS_CHECK: the keys have not been
