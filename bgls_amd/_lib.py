@@ -31,6 +31,10 @@ SIGNATURES = {
     "bgls_verify_aggregate": (ci, [ci, u8p, u8p, u8p, u64p, sz, ci]),
     "bgls_verify_aggregate_batch": (ci, [ci, u8p, u8p, u64p, sz, u8p, u64p, ci, u8p, u8p]),
     "bgls_verify_aggregate_batch_dev": (ci, [ci, vp, vp, u64p, sz, vp, sz, sz, ci, u8p, u8p, vp]),
+    "bgls_group_messages": (ci, [u8p, u64p, sz, u32p, ctypes.POINTER(sz)]),
+    "bgls_group_messages_dev": (ci, [vp, sz, sz, sz, vp, ctypes.POINTER(sz), vp]),
+    "bgls_verify_aggregate_grouped": (ci, [ci, u8p, u8p, u8p, u64p, sz, ctypes.POINTER(sz), u8p]),
+    "bgls_verify_aggregate_grouped_dev": (ci, [ci, vp, vp, vp, sz, sz, sz, ctypes.POINTER(sz), u8p, vp]),
     "bgls_hash_to_g1_keyed": (ci, [ci, ci, u8p, u8p, u64p, sz, u8p]),
     "bgls_verify_aggregate_distinct": (ci, [ci, u8p, u8p, u8p, u64p, sz]),
     "bgls_verify_aggregate_distinct_h": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, u8p]),

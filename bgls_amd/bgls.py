@@ -104,6 +104,44 @@ def KoskVerifyAggregateSignature(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:
     return _verify_agg(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs], True)
 
 
+def GroupMessages(msgs):
+    """(group_of, n_groups): group_of[i] is the number of the group of msgs[i]; two messages share a group iff their bytes are equal, and
+    groups are numbered in the order of their first occurrence (bgls_group_messages: the grouping runs on the device)."""
+    ms = [bytes(m) for m in msgs]
+    n = len(ms)
+    group_of = (ctypes.c_uint32 * max(n, 1))()
+    n_groups = ctypes.c_size_t(0)
+    rc = _lib.load().bgls_group_messages(_lib.buf(b"".join(ms)), _offsets(ms), n, group_of, ctypes.byref(n_groups))
+    if rc != 0:
+        raise RuntimeError("bgls_group_messages: %d %s" % (rc, _lib.last_error()))
+    return list(group_of)[:n], n_groups.value
+
+
+def VerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):
+    """KoskVerifyAggregateSignature's body (verifyAggSig with allowDuplicates = true, bgls/blsKosk.go:100-106) with one hash and one
+    pairing per DISTINCT message: the keys of the signers of one message are summed first (bgls_verify_aggregate_grouped).  Same verdict
+    as _verify_agg(..., True); messages are grouped by exact bytes; there is no duplicate rule.  keys: a list of G2 Points -- for a
+    resident KeySet use the signer-bitmap calls (VerifyMultiSignaturesBySubset, AggregateKeysBySubset)."""
+    if isinstance(keys, KeySet):
+        raise TypeError("VerifyAggregateSignatureGrouped takes a list of keys; over a KeySet use the signer-bitmap calls "
+                        "(VerifyMultiSignaturesBySubset / AggregateKeysBySubset)")
+    if len(keys) != len(msgs):                       # bgls/bgls.go:95-97
+        return False
+    if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+        return False
+    for k in keys:
+        if not (isinstance(k, Point) and k.curve is curve and k.group == G2):
+            return False
+    ms = [bytes(m) for m in msgs]
+    rc = _lib.load().bgls_verify_aggregate_grouped(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), _lib.buf(b"".join(ms)),
+                                                   _offsets(ms), len(ms), None, None)
+    return rc == 1                                   # every failure collapses to false (bgls.go:115-118)
+
+
+def KoskVerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:100-106
+    return VerifyAggregateSignatureGrouped(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs])
+
+
 def _verify_agg_batch(curve, aggsigs, keys_per_instance, msgs_per_instance, allow_duplicates):
     """One bgls_verify_aggregate_batch call for every instance made of Points of this curve; an instance that is not (mismatched lengths,
     a foreign point, a KeySet) gets what _verify_agg says about it alone.  A call that fails as a whole (an encoding or hashing error

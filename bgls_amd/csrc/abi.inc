@@ -50,6 +50,52 @@ int bgls_verify_aggregate_batch_dev(int curve, const void* d_sigs, const void* d
   DISPATCH(curve, verify_aggregate_batch_dev_t<CV>(d_sigs, d_keys, inst_off, n_inst, d_msgs, msg_len, msg_stride, allow_duplicates, verdicts, gt_out, stream));
 } BGLS_ABI_GUARD
 
+// ---- aggregate verification that pairs once per distinct message: the grouping by exact bytes, and the verification on top of it
+int bgls_group_messages(const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint32_t* group_of, size_t* n_groups) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) {
+    if (n_groups) *n_groups = 0;
+    return 0;
+  }
+  if (!msg_off || !group_of) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (msg_off[n] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  return group_messages_t(msg_blob, msg_off, n, group_of, n_groups);
+} BGLS_ABI_GUARD
+
+int bgls_group_messages_dev(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_group_of, size_t* n_groups,
+                            void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) {
+    if (n_groups) *n_groups = 0;
+    return 0;
+  }
+  if (!d_group_of || (msg_len && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (msg_stride < msg_len) return fail(BGLS_ERR_ARG, "msg_stride below msg_len");
+  return group_messages_dev_t(d_msgs, msg_len, msg_stride, n, d_group_of, n_groups, stream);
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_grouped(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
+                                  size_t n, size_t* n_groups, uint8_t* gt_out) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (!sig || !msg_off || (n && !keys)) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n, 0))) return rc;
+  if (msg_off[n] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n_groups) *n_groups = 0;
+  DISPATCH(curve, verify_aggregate_grouped_t<CV>(sig, keys, msg_blob, msg_off, n, n_groups, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_grouped_dev(int curve, const void* d_sig, const void* d_keys, const void* d_msgs, size_t msg_len,
+                                      size_t msg_stride, size_t n, size_t* n_groups, uint8_t* gt_out, void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (!d_sig || (n && (!d_keys || (msg_len && !d_msgs)))) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n && msg_stride < msg_len) return fail(BGLS_ERR_ARG, "msg_stride below msg_len");
+  if (n_groups) *n_groups = 0;
+  DISPATCH(curve, verify_aggregate_grouped_dev_t<CV>(d_sig, d_keys, d_msgs, msg_len, msg_stride, n, n_groups, gt_out, stream));
+} BGLS_ABI_GUARD
+
 // ---- distinct messages (bgls/blsDistinctMessage.go) and proofs of possession (bgls/blsKosk.go:59-69): the hash inputs are built on the device
 int bgls_verify_aggregate_distinct(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off, size_t n) try {
   if (n >= MAX_BATCH) return too_large();

@@ -40,6 +40,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 #include "launch.hpp"
 #include "launch_tail.hpp"
 #include "sumsel.hpp"
+#include "msggroup.hpp"
 #include "../../include/bgls_hip.h"
 
 using namespace bgls;

@@ -312,10 +312,11 @@ bool sum_pairs() { return !legacy(LG_SUM); }
 // ST_AMS_MSGS by the batched accountable-subgroup multisignatures only (Engine::miller_ams: the assembly of the hash inputs)
 // ST_RLC by the combined multi-signature check only (verify_sets_combined_run: the coefficients, k_rlc_pair, the per-group signature sums)
 // ST_KEY_MSGS by the distinct-message and authentication checks only (Engine::key_msgs: the hash inputs built from the keys on the device)
+// ST_GROUP by the grouping of messages only (Engine::group_messages: table, numbering, index list, work items, compaction)
 enum { ST_DUP = 0, ST_H2C, ST_MILLER, ST_REDUCE, ST_FINAL, ST_SUM, ST_SUM_MAIN, ST_SCATTER, ST_EPI, ST_BB_KEYS, ST_HAE_KEYS, ST_AMS_MSGS, ST_KEY_MSGS, ST_RLC,
-       ST_NUM };
+       ST_GROUP, ST_NUM };
 const char* const STAGE_NAMES[ST_NUM] = {"dup_check", "h2c", "miller", "reduce", "final_exp", "sum_points", "sum_main", "scatter", "epilogue", "bb_keys",
-                                         "hae_keys", "ams_msgs", "key_msgs", "rlc"};
+                                         "hae_keys", "ams_msgs", "key_msgs", "rlc", "group"};
 
 // roctx ranges around the stages (SURVEY section 5: "roctx ranges around H2C / Miller / reduce / final-exp"), behind bgls_profile_enable like
 // the event timers: `rocprofv3 --marker-trace` then shows bgls:h2c, bgls:miller, ... on the host timeline next to the kernels.  The
@@ -340,7 +341,8 @@ Roctx& roctx() {
   return r;
 }
 const char* const STAGE_RANGES[ST_NUM] = {"bgls:dup_check", "bgls:h2c", "bgls:miller", "bgls:reduce", "bgls:final_exp", "bgls:sum_points", "bgls:sum_main",
-                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs", "bgls:key_msgs", "bgls:rlc"};
+                                          "bgls:scatter", "bgls:epilogue", "bgls:bb_keys", "bgls:hae_keys", "bgls:ams_msgs", "bgls:key_msgs", "bgls:rlc",
+                                          "bgls:group"};
 
 struct Scope {  // brackets the launches of one stage with events (and a roctx range) when profiling is on; on = false: part of the caller's stage
   Ctx& c; hipStream_t st; int stage; hipEvent_t a = nullptr; bool ranged = false;
@@ -415,6 +417,133 @@ struct Engine {
     Scope sc(c, st, ST_KEY_MSGS);
     kl::key_msgs(st, C::CURVE_ID, mode, d_keys, n, mv, (uint8_t*)blob, cap, (uint64_t*)ooff, d_flags);
     HIPCHK(hipGetLastError());
+    return 0;
+  }
+
+  // The groups of n >= 1 messages by exact bytes (k_msggroup.hip; bgls_group_messages, bgls_verify_aggregate_grouped).  d = the number of
+  // distinct messages; group_of[i] = the group of message i, numbered in the order of first occurrence (written to d_group_of where the
+  // caller gives a device array, else to the workspace).  plan = true adds what the verification needs: the index list idx sorted by group
+  // (group g: start[g] .. start[g + 1]), the n_items work items {lo, hi} of the indexed key sum with item_start (d + 1 offsets: the
+  // partials of group g), the n_multi groups of several items (multi) with their runs of partials as the work items of the second pass
+  // (joins), and reps: the d representative messages as an ordinary view
+  // (msg_bytes: an upper bound of the bytes of all n messages).  Workspaces (DESIGN.md section 5): the table and the first occurrences in
+  // WS_TABLE, every array of 32-bit words in WS_MSM_LIST, of 64-bit words in WS_SEG_OFF, the compacted messages in WS_KEYED_BLOB /
+  // WS_KEYED_OFF.  Table, counters, cursors and the size word are reset here; everything else is written before it is read.  The host
+  // waits once for d and, with plan, once more for the item count: the launches that follow are sized by them.
+  struct Groups {
+    size_t d = 0, n_items = 0, n_multi = 0;
+    const uint32_t *group_of = nullptr, *idx = nullptr, *start = nullptr, *multi = nullptr;
+    const void *items = nullptr, *joins = nullptr;
+    const uint64_t* item_start = nullptr;
+    MsgView reps = {nullptr, nullptr, 0, 0};
+  };
+  static int group_messages(Ctx& c, hipStream_t st, MsgView mv, size_t msg_bytes, size_t n, uint32_t* d_group_of, bool plan, Groups* out) {
+    if (n >= MAX_BATCH) return too_large();
+    if (c.res_pending) return in_flight();                  // the pinned result words carry d and the item count to the host
+    size_t cap = 2;
+    while (cap < 2 * n) cap <<= 1;
+    const size_t tiles = kl::scan_tiles(n + 1);
+    const uint32_t chunk = msggroup_chunk(n);
+    const size_t most_multi = n / chunk + 1;                // a group of several items has more than `chunk` keys
+    size_t w32 = 0, w64 = 0;
+    auto take = [](size_t& at, size_t words) { const size_t r = at; at += (words + 63) & ~(size_t)63; return r; };
+    const size_t o_slot = take(w32, n), o_rep = take(w32, n), o_rank = take(w32, n + 1), o_group = take(w32, d_group_of ? 0 : n), o_idx = take(w32, n),
+                 o_repidx = take(w32, n), o_count = take(w32, n), o_cursor = take(w32, n), o_start = take(w32, n + 1), o_nitems = take(w32, n),
+                 o_items = take(w32, 2 * (msggroup_max_items(n, n, chunk) + 1)), o_joins = take(w32, 2 * most_multi), o_multi = take(w32, most_multi),
+                 o_bsum = take(w32, tiles + 1), o_meta = take(w32, 8);
+    const size_t o_istart = take(w64, n + 1), o_lens = take(w64, n), o_bsum64 = take(w64, tiles + 1);
+    void *tab, *a32, *a64, *blob = nullptr, *ooff = nullptr;
+    int rc;
+    if ((rc = c.get(WS_TABLE, cap * 8, &tab))) return rc;
+    if ((rc = c.get(WS_MSM_LIST, w32 * 4, &a32))) return rc;
+    if ((rc = c.get(WS_SEG_OFF, w64 * 8, &a64))) return rc;
+    if (plan && (rc = c.get(WS_KEYED_BLOB, mv.off ? msg_bytes : n * mv.len, &blob))) return rc;
+    if (plan && mv.off && (rc = c.get(WS_KEYED_OFF, (n + 1) * 8, &ooff))) return rc;
+    uint32_t *table = (uint32_t*)tab, *first = table + cap, *u = (uint32_t*)a32;
+    uint64_t* v = (uint64_t*)a64;
+    uint32_t* group_of = d_group_of ? d_group_of : u + o_group;
+    Scope sc(c, st, ST_GROUP);
+    HIPCHK(hipMemsetAsync(table, 0, cap * 4, st));
+    HIPCHK(hipMemsetAsync(first, 0xFF, cap * 4, st));
+    kl::grp_resolve(st, mv, n, table, (uint32_t)(cap - 1), first, u + o_slot, dup_seed());
+    kl::grp_mark(st, n, u + o_slot, first, u + o_rep);
+    kl::scan_excl<uint32_t, uint32_t>(st, u + o_rep, n, u + o_bsum, u + o_rank);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&c.h_res[4], u + o_rank + n, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t d = c.h_res[4];
+    if (d == 0 || d > n) return fail(BGLS_ERR_HIP, "message grouping: inconsistent group count");
+    HIPCHK(hipMemsetAsync(u + o_count, 0, d * 4, st));
+    kl::grp_assign(st, n, u + o_rep, u + o_rank, u + o_slot, table, u + o_repidx);
+    kl::grp_groups(st, n, u + o_slot, table, group_of, u + o_count);
+    kl::scan_excl<uint32_t, uint32_t>(st, u + o_count, d, u + o_bsum, u + o_start);
+    HIPCHK(hipGetLastError());
+    out->d = d;
+    out->group_of = group_of;
+    if (!plan) return 0;
+    HIPCHK(hipMemsetAsync(u + o_cursor, 0, d * 4, st));
+    HIPCHK(hipMemsetAsync(u + o_meta, 0, 8 * 4, st));
+    kl::grp_scatter(st, n, group_of, u + o_start, u + o_cursor, u + o_idx);
+    kl::grp_nitems(st, d, u + o_start, chunk, u + o_nitems, u + o_meta);
+    kl::scan_excl<uint32_t, uint64_t>(st, u + o_nitems, d, v + o_bsum64, v + o_istart);
+    kl::grp_items(st, d, u + o_start, v + o_istart, chunk, u + o_items, u + o_joins, u + o_multi, u + o_meta);
+    HIPCHK(hipMemcpyAsync(&c.h_res[8], u + o_meta, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&c.h_res[6], v + o_istart + d, 8, hipMemcpyDeviceToHost, st));
+    if (mv.off) {
+      kl::grp_lens(st, mv, d, u + o_repidx, v + o_lens);
+      kl::scan_excl<uint64_t, uint64_t>(st, v + o_lens, d, v + o_bsum64, (uint64_t*)ooff);
+      kl::grp_compact(st, mv, d, u + o_repidx, (const uint64_t*)ooff, 0, (uint8_t*)blob);
+      out->reps = {(const uint8_t*)blob, (const uint64_t*)ooff, 0, 0};
+    } else {
+      kl::grp_compact(st, mv, d, u + o_repidx, nullptr, mv.len, (uint8_t*)blob);
+      out->reps = {(const uint8_t*)blob, nullptr, mv.len, mv.len};
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t n_items;
+    memcpy(&n_items, &c.h_res[6], 8);
+    const size_t largest = c.h_res[8], n_multi = c.h_res[9];
+    if (n_items < d || n_items > msggroup_max_items(n, d, chunk) || largest == 0 || largest > n || n_multi >= most_multi || (n_multi != 0) != (largest > chunk))
+      return fail(BGLS_ERR_HIP, "message grouping: inconsistent work plan");
+    out->n_items = (size_t)n_items;
+    out->n_multi = n_multi;
+    out->multi = u + o_multi;
+    out->joins = u + o_joins;
+    out->idx = u + o_idx;
+    out->start = u + o_start;
+    out->items = u + o_items;
+    out->item_start = v + o_istart;
+    return 0;
+  }
+
+  // The d key sums of the groups as wire bytes at *d_sums (WS_SEG_KEYS): the indexed main pass, one block and one partial per work item
+  // (k_sumpairidx_main), the partials to wire bytes, and each group's sum to its place -- the partial itself where the group has one item,
+  // else the sum of its partials (contiguous by construction) from a second pass of the same kernel, one block per such group, over the
+  // partials' wire bytes.  There are fewer than n / chunk + 1 such groups.  A bad key anywhere sets FLAG_ENC.
+  // Layout of WS_SEG_KEYS: d + 1 key sums | n_items partials | n_multi joined sums; WS_JAC_A: n_items partials, WS_JAC_B: n_multi.
+  static int sum_groups(Ctx& c, hipStream_t st, const uint8_t* d_keys, const Groups& g, const uint8_t** d_sums, uint32_t* d_flags) {
+    const size_t JB = kl::jac_bytes<C>(BGLS_G2);
+    if (g.n_items > ((size_t)1 << 30)) return fail(BGLS_ERR_ARG, "too many work items for one call");
+    void *ja, *jb, *ks;
+    int rc;
+    Scope sc(c, st, ST_SUM);
+    if ((rc = c.get(WS_JAC_A, (g.n_items + 1) * JB, &ja))) return rc;
+    if ((rc = c.get(WS_JAC_B, (g.n_multi + 1) * JB, &jb))) return rc;
+    if ((rc = c.get(WS_SEG_KEYS, (g.d + 1 + g.n_items + g.n_multi) * G2B, &ks))) return rc;
+    uint8_t *sums = (uint8_t*)ks, *parts = sums + (g.d + 1) * G2B, *joined = parts + g.n_items * G2B;
+    {
+      Scope scm(c, st, ST_SUM_MAIN);
+      kl::sumpairidx_main<C>(st, d_keys, g.idx, g.items, g.n_items, ja, d_flags);
+    }
+    kl::jac_to_bytes<C>(st, BGLS_G2, ja, g.n_items, parts);
+    kl::grp_pick(st, g.d, g.item_start, parts, G2B, sums);
+    if (g.n_multi) {
+      kl::sumpairidx_main<C>(st, parts, nullptr, g.joins, g.n_multi, jb, d_flags);
+      kl::jac_to_bytes<C>(st, BGLS_G2, jb, g.n_multi, joined);
+      kl::grp_place(st, g.n_multi, g.multi, joined, G2B, sums);
+    }
+    HIPCHK(hipGetLastError());
+    *d_sums = sums;
     return 0;
   }
 

@@ -111,6 +111,81 @@ int verify_aggregate_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* b
   return E::finalize(c, st, (const uint8_t*)d_part, 1, 1, (const uint32_t*)d_flags, nullptr);
 }
 
+// ---- aggregate verification that pairs once per distinct message (bgls_group_messages, bgls_verify_aggregate_grouped) ----
+// the grouping alone: group_of to the host (h_group_of) or left in the caller's device array (d_group_of)
+int group_messages_run(Ctx& c, hipStream_t st, MsgView mv, size_t n, uint32_t* h_group_of, uint32_t* d_group_of, size_t* n_groups) {
+  typedef Engine<BN254> E;                                 // curve-independent
+  E::Groups g;
+  int rc;
+  if ((rc = E::group_messages(c, st, mv, 0, n, d_group_of, false, &g))) return rc;
+  if (h_group_of) HIPCHK(hipMemcpyAsync(h_group_of, g.group_of, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c.collect();
+  if (n_groups) *n_groups = g.d;
+  return 0;
+}
+int group_messages_t(const uint8_t* blob, const uint64_t* off, size_t n, uint32_t* group_of, size_t* n_groups) {
+  Call k;
+  if (k.rc) return k.rc;
+  int rc;
+  MsgView mv;
+  if ((rc = upload_msgs(k.c, k.st, blob, off, n, &mv))) return rc;
+  return group_messages_run(k.c, k.st, mv, n, group_of, nullptr, n_groups);
+}
+int group_messages_dev_t(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_group_of, size_t* n_groups, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return group_messages_run(k.c, k.st, mv, n, nullptr, (uint32_t*)d_group_of, n_groups);
+}
+
+// the grouping, the indexed key sum into d key sums, then the sibling's product over the d (key sum, representative message) pairs
+// (no duplicate rule) and ONE final exponentiation.  msg_bytes: an upper bound of the bytes of the n messages.
+template <class C>
+int verify_aggregate_grouped_run(Ctx& c, hipStream_t st, const uint8_t* d_sig, const uint8_t* d_keys, MsgView mv, size_t msg_bytes, size_t n,
+                                 size_t* n_groups, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  if (c.res_pending) return in_flight();
+  int rc;
+  void *d_flags, *d_part;
+  if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
+  if ((rc = c.get(WS_PART, E::GTB, &d_part))) return rc;
+  HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
+  typename E::Groups g;
+  const uint8_t* d_sums = d_keys;
+  if (n) {
+    if ((rc = E::group_messages(c, st, mv, msg_bytes, n, nullptr, true, &g))) return rc;
+    if ((rc = E::sum_groups(c, st, d_keys, g, &d_sums, (uint32_t*)d_flags))) return rc;
+    mv = g.reps;
+  }
+  if ((rc = E::miller_product(c, st, d_sig, d_sums, mv, g.d, 0, (uint8_t*)d_part, (uint32_t*)d_flags))) return rc;
+  if (n_groups) *n_groups = g.d;
+  return E::finalize(c, st, (const uint8_t*)d_part, 1, 1, (const uint32_t*)d_flags, gt_out);
+}
+template <class C>
+int verify_aggregate_grouped_t(const uint8_t* sig, const uint8_t* keys, const uint8_t* blob, const uint64_t* off, size_t n, size_t* n_groups,
+                               uint8_t* gt_out) {
+  typedef Engine<C> E;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  int rc;
+  MsgView mv;
+  void *d_sig, *d_keys;
+  if ((rc = upload_msgs(c, k.st, blob, off, n, &mv))) return rc;
+  if ((rc = c.put(k.st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
+  if ((rc = c.put(k.st, WS_IN_B, keys, n * E::G2B, &d_keys))) return rc;
+  return verify_aggregate_grouped_run<C>(c, k.st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n ? off[n] : 0, n, n_groups, gt_out);
+}
+template <class C>
+int verify_aggregate_grouped_dev_t(const void* d_sig, const void* d_keys, const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n,
+                                   size_t* n_groups, uint8_t* gt_out, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_aggregate_grouped_run<C>(k.c, k.st, (const uint8_t*)d_sig, (const uint8_t*)d_keys, mv, n * msg_len, n, n_groups, gt_out);
+}
+
 // What a call with one verdict per item hands back, and the two things in which the Boneh-Boyen form differs from the others.
 struct BatchOut {
   uint8_t* verdicts;                 // n bytes, 1 / 0

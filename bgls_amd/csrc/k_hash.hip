@@ -4,6 +4,7 @@
 #include "dev_common.hpp"
 #include "h2c.hpp"
 #include "launch.hpp"
+#include "msggroup.hpp"
 #include "rx_pow.hpp"
 #include "rx_jac1.hpp"
 #include "h2c_x.hpp"
@@ -11,20 +12,8 @@
 using namespace bgls;
 
 // ---- duplicate-message scan: open-addressing table of (index+1), exact byte comparison ----
-// `seed`: drawn by the host per process and call (engine_core.inc dup_scan).  The slot of a record must not be predictable from its bytes: an
-// unseeded FNV can be inverted, and 2^20 chosen messages that share one slot turn the scan into 2^40 probes (the reference's Go map is
-// seeded per process for the same reason, bgls/bgls.go:139-150).
-__device__ __forceinline__ uint64_t msg_hash64(const uint8_t* p, size_t n, uint64_t seed) {
-  uint64_t h = 0xcbf29ce484222325ull ^ seed;
-  for (size_t i = 0; i < n; ++i) {
-    h ^= p[i];
-    h *= 0x100000001b3ull;
-  }
-  h ^= h >> 29;
-  h *= 0xbf58476d1ce4e5b9ull;
-  h ^= h >> 32;
-  return h;
-}
+// msg_hash64 (msggroup.hpp, shared with the grouping kernels of k_msggroup.hip) places a record; its `seed` is drawn by the host per
+// process and call (engine_core.inc dup_scan).
 
 // bucket / n_buckets (n_buckets > 1): only the records whose first byte is `bucket` mod n_buckets enter the table -- equal records
 // share a bucket, so n_buckets scans (one per rank of a multi-GPU verification, over the all-gathered digests) find exactly what

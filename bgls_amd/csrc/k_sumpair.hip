@@ -1,6 +1,7 @@
 // G2 key sums (the main pass of AggregatePoints, curves/curve.go:73-121) on LANE PAIRS in the carry-free form: rx_jacpair.hpp.
 //   k_sumpair_main      pair t adds keys t, t + T, t + 2T, ... (T = lane pairs in the launch) into its own Jacobian sum
 //   k_sumpairseg_main   the same for nsets key sets in one launch (KoskVerifyBatchMultiSignature, bgls/blsKosk.go:126-133)
+//   k_sumpairidx_main   the same over an index list cut into work items, one block each (bgls_verify_aggregate_grouped)
 // The 32 sums of a block (one wave) are then added in the block, five levels through LDS (general Jacobian additions shared by
 // the two lane pairs whose sums they join), so that a block leaves ONE partial: 3072 for 2^20 keys instead of 98 304, and the tree above them (k_sum_coop:
 // one wave per addition) starts where it has few enough additions to be worth a wave each.  Partials leave in the library's
@@ -195,6 +196,28 @@ __global__ void __launch_bounds__(64, 3) k_sumpairseg_main(const uint8_t* pts, c
   if (threadIdx.x < 2) sumpair_store<C>(out + blockIdx.x, acc, odd);      // partials of set b: blocks b * per .. (b + 1) * per - 1
 }
 
+// k_sumpairseg_main's body over an INDEX LIST, one work item per block (bgls_verify_aggregate_grouped: the keys of the signers of one
+// message are scattered over the caller's key array).  Item b = positions items[b].x .. items[b].y of idx (msggroup.hpp: at most
+// msggroup_chunk(n) of them, all of one group); lane pair t adds keys idx[lo + t], idx[lo + t + 32], ...  One partial per item, in item
+// order: the partials of a group are contiguous.  The time follows the number of keys, not the shape of the group sizes.  idx == nullptr:
+// the positions are the keys -- the second pass, whose "keys" are the wire bytes of a group's partials and whose items are whole groups.
+template <class C>
+__global__ void __launch_bounds__(64, 3) k_sumpairidx_main(const uint8_t* pts, const uint32_t* idx, const uint2* items, Jac<F2<C>>* out, uint32_t* flags) {
+  const uint2 it = items[blockIdx.x];
+  const bool odd = threadIdx.x & 1;
+  JacP<C> acc = jacp_inf<C>();
+  bool bad = false;
+#pragma unroll 1
+  for (uint32_t k = it.x + (threadIdx.x >> 1); k < it.y; k += 32) {
+    AffP<C> q;
+    bad = !sumpair_fetch<C, 0>(q, pts, idx ? idx[k] : k, odd) || bad;
+    acc = jacp_madd<C>(acc, q, odd);
+  }
+  if (bad && !odd) atomicOr(flags, FLAG_ENC);
+  acc = sumpair_block_tree<C>(acc, odd);
+  if (threadIdx.x < 2) sumpair_store<C>(out + blockIdx.x, acc, odd);
+}
+
 // ---- key sums by signer bitmap over a key set's sum-ready records (bgls_verify_multi_subsets_h, bgls_aggregate_subsets_h) ----
 // Planning pass, one wave per set: the row's popcount over [0, n) and its mode to plan[2 b], plan[2 b + 1] (1 = complement: the block
 // adds the negated keys that are NOT selected, and block 0 of the set the whole-set sum), FLAG_SUBSET_STRAY where the row has a bit at a
@@ -369,6 +392,14 @@ void sumpairseg_main(hipStream_t st, const uint8_t* pts, const uint64_t* off, si
   typedef typename SumForm<C>::type X;
   k_sumpairseg_main<X><<<(unsigned)(nsets * (P / 32)), 64, 0, st>>>(pts, off, P, (Jac<F2<X>>*)out, flags);
 }
+// n_items blocks, one Jacobian partial each; items: n_items pairs {lo, hi} of positions in idx (uint2)
+template <class C>
+void sumpairidx_main(hipStream_t st, const uint8_t* pts, const uint32_t* idx, const void* items, size_t n_items, void* out, uint32_t* flags) {
+  typedef typename SumForm<C>::type X;
+  k_sumpairidx_main<X><<<(unsigned)n_items, 64, 0, st>>>(pts, idx, (const uint2*)items, (Jac<F2<X>>*)out, flags);
+}
+template void sumpairidx_main<BN254>(hipStream_t, const uint8_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
+template void sumpairidx_main<BLS381>(hipStream_t, const uint8_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
 void sumsel_plan(hipStream_t st, const uint32_t* rows, size_t stride_w, size_t n, size_t nsets, int mode, uint32_t* plan, uint32_t* flags) {
   k_sumsel_plan<<<(unsigned)nsets, 64, 0, st>>>(rows, stride_w, n, mode, plan, flags);
 }

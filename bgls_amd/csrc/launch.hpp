@@ -20,6 +20,24 @@ void h2c_bn(hipStream_t st, MsgView mv, size_t n, uint32_t* lists, uint32_t* cou
 void h2c_bls(hipStream_t st, MsgView mv, size_t n, Jac<F1<BLS381>>* pts, uint32_t* kinds, Aff<F1<BLS381>>* out, bool raw);   // pts: 2n Jacobian work items
 void blake2x_expand(hipStream_t st, const uint64_t* root, uint32_t xof_len, uint8_t* out);
 
+// ---- k_msggroup.hip   (grouping of messages by exact bytes; the stages in the order Engine::group_messages runs them, see the unit's head)
+// scan_excl: out[0 .. n] = the exclusive prefix sums of in[0 .. n) and the total; bsum: scan_tiles(n) words of scratch
+size_t scan_tiles(size_t n);
+template <class TI, class TO> void scan_excl(hipStream_t st, const TI* in, size_t n, TO* bsum, TO* out);
+void grp_resolve(hipStream_t st, MsgView mv, size_t n, uint32_t* table, uint32_t mask, uint32_t* first, uint32_t* slot_of, uint64_t seed);
+void grp_mark(hipStream_t st, size_t n, const uint32_t* slot_of, const uint32_t* first, uint32_t* rep);
+void grp_assign(hipStream_t st, size_t n, const uint32_t* rep, const uint32_t* rank, const uint32_t* slot_of, uint32_t* table, uint32_t* rep_idx);
+void grp_groups(hipStream_t st, size_t n, const uint32_t* slot_of, const uint32_t* table, uint32_t* group_of, uint32_t* count);
+void grp_scatter(hipStream_t st, size_t n, const uint32_t* group_of, const uint32_t* start, uint32_t* cursor, uint32_t* idx);
+void grp_nitems(hipStream_t st, size_t d, const uint32_t* start, uint32_t chunk, uint32_t* nitems, uint32_t* meta);      // meta[0] <- max(meta[0], largest group)
+// items: {lo, hi} per item; joins / multi: the meta[1] groups of several items, {first, last + 1} of their partials and the group (meta[1] from 0)
+void grp_items(hipStream_t st, size_t d, const uint32_t* start, const uint64_t* item_start, uint32_t chunk, void* items, void* joins, uint32_t* multi, uint32_t* meta);
+// key sums to their places (rec_bytes each, a multiple of 16): a one-item group's partial from parts[item_start[g]]; joined sum k to group multi[k]
+void grp_pick(hipStream_t st, size_t d, const uint64_t* item_start, const uint8_t* parts, size_t rec_bytes, uint8_t* sums);
+void grp_place(hipStream_t st, size_t m, const uint32_t* multi, const uint8_t* joined, size_t rec_bytes, uint8_t* sums);
+void grp_lens(hipStream_t st, MsgView mv, size_t d, const uint32_t* rep_idx, uint64_t* lens);
+void grp_compact(hipStream_t st, MsgView mv, size_t d, const uint32_t* rep_idx, const uint64_t* out_off, size_t out_stride, uint8_t* out);
+
 // ---- k_points.hip   (group = BGLS_G1 / BGLS_G2; Jacobian workspaces are passed as void*)
 template <class C> void g1_to_bytes(hipStream_t st, const Aff<F1<C>>* in, size_t n, uint8_t* out);
 template <class C> void g1_parse(hipStream_t st, const uint8_t* in, size_t n, int negate, Aff<F1<C>>* out, uint32_t* flags);
@@ -28,6 +46,9 @@ template <class C> void sumseg_main(hipStream_t st, int group, const uint8_t* pt
 // ---- k_sumpair.hip   (G2 key sums on lane pairs, carry-free limbs: rx_jacpair.hpp)
 template <class C> void sumpair_main(hipStream_t st, int src, const uint8_t* pts, size_t n, unsigned partials, void* out, uint32_t* flags);
 template <class C> void sumpairseg_main(hipStream_t st, const uint8_t* pts, const uint64_t* off, size_t nsets, unsigned P, void* out, uint32_t* flags);
+// items: n_items pairs {lo, hi} (uint2) of positions in the index list idx (nullptr: the positions themselves), one block and one Jacobian
+// partial per item (msggroup.hpp)
+template <class C> void sumpairidx_main(hipStream_t st, const uint8_t* pts, const uint32_t* idx, const void* items, size_t n_items, void* out, uint32_t* flags);
 template <class C> void sum_wave(hipStream_t st, int group, const void* in, size_t n, void* out);
 template <class C> void sum_pair(hipStream_t st, int group, const void* in, size_t n, void* out);
 template <class C> void sum_coop(hipStream_t st, const void* in, size_t n, void* out);        // G2, one wave per addition (jac_coop.hpp)

@@ -56,6 +56,50 @@ inline bool KoskVerifyAggregateSignature(const CurveSystem* curve, const Point& 
   }
   return verifyAggSig(curve, aggsig, keys, m2, true);
 }
+
+// group_of[i] = the number of the group of msgs[i]: two messages share a group iff their bytes are equal, groups are numbered in the order
+// of their first occurrence (bgls_group_messages: the grouping runs on the device).  false: the call failed, see bgls_last_error().
+inline bool GroupMessages(const std::vector<Bytes>& msgs, std::vector<uint32_t>& group_of, size_t& n_groups) {
+  Bytes blob;
+  std::vector<uint64_t> off(msgs.size() + 1, 0);
+  for (size_t i = 0; i < msgs.size(); ++i) {
+    off[i] = blob.size();
+    blob.insert(blob.end(), msgs[i].begin(), msgs[i].end());
+  }
+  off[msgs.size()] = blob.size();
+  group_of.assign(msgs.size(), 0);
+  n_groups = 0;
+  return bgls_group_messages(blob.data(), off.data(), msgs.size(), group_of.data(), &n_groups) == 0;
+}
+// verifyAggSig with allowDuplicates = true (KoskVerifyAggregateSignature's body, bgls/blsKosk.go:100-106) with one hash and one pairing per
+// DISTINCT message: the keys of the signers of one message are summed first (bgls_verify_aggregate_grouped).  Same verdict; messages are
+// grouped by exact bytes; no duplicate rule.  For keys resident in a KeySet use its signer-bitmap calls (VerifyMultiSignaturesBySubset).
+inline bool VerifyAggregateSignatureGrouped(const CurveSystem* curve, const Point& aggsig, const std::vector<Point>& keys,
+                                            const std::vector<Bytes>& msgs, size_t* n_groups = nullptr) {
+  if (keys.size() != msgs.size()) return false;
+  if (aggsig.curve != curve || aggsig.group != BGLS_G1) return false;
+  Bytes kb, blob;
+  std::vector<uint64_t> off(msgs.size() + 1, 0);
+  for (size_t i = 0; i < keys.size(); ++i) {
+    if (keys[i].curve != curve || keys[i].group != BGLS_G2) return false;
+    kb.insert(kb.end(), keys[i].raw.begin(), keys[i].raw.end());
+    off[i] = blob.size();
+    blob.insert(blob.end(), msgs[i].begin(), msgs[i].end());
+  }
+  off[msgs.size()] = blob.size();
+  return bgls_verify_aggregate_grouped(curve->id, aggsig.raw.data(), kb.data(), blob.data(), off.data(), keys.size(), n_groups, nullptr) == 1;
+}
+// bgls/blsKosk.go:100-106, grouped
+inline bool KoskVerifyAggregateSignatureGrouped(const CurveSystem* curve, const Point& aggsig, const std::vector<Point>& keys,
+                                                const std::vector<Bytes>& msgs, size_t* n_groups = nullptr) {
+  std::vector<Bytes> m2;
+  for (const Bytes& m : msgs) {
+    Bytes x(1, 1);
+    x.insert(x.end(), m.begin(), m.end());
+    m2.push_back(x);
+  }
+  return VerifyAggregateSignatureGrouped(curve, aggsig, keys, m2, n_groups);
+}
 // verifyMultiSignature, bgls/bgls.go:89-92
 inline bool verifyMultiSignature(const CurveSystem* curve, const Point& aggsig, const std::vector<Point>& keys, const Bytes& msg) {
   if (aggsig.curve != curve || aggsig.group != BGLS_G1) return false;      // a nil / foreign aggsig is `false`

@@ -99,6 +99,39 @@ int bgls_verify_aggregate_batch(int curve, const uint8_t* sigs, const uint8_t* k
                                 const uint8_t* msg_blob, const uint64_t* msg_off, int allow_duplicates, uint8_t* verdicts,
                                 uint8_t* gt_out);
 
+/* ---- aggregate verification that pairs once per DISTINCT message ---------------------------------------------------------------
+ * KoskVerifyAggregateSignature (bgls/blsKosk.go:100-106) lets many signers sign the same message.  By bilinearity
+ * prod_i e(H(m_i), pk_i) = prod over the distinct messages m of e(H(m), sum of the keys of the signers of m), so n signers over d distinct
+ * messages need d hashes, d + 1 Miller loops and n G2 additions instead of n hashes and n + 1 Miller loops.  The caller passes the
+ * reference's own argument shape, flat keys[] and msgs[]; the grouping is done on the device.
+ *
+ * bgls_group_messages: group_of[i] = number of the group of message i.  Two messages share a group iff they are byte-identical (same
+ * length, same bytes).  Groups are numbered 0 .. *n_groups - 1 in the order of their FIRST occurrence, so the result is a function of
+ * the input alone.  n_groups may be NULL.  n == 0 returns 0 with *n_groups = 0 and touches no other pointer.  The _dev form takes n
+ * messages of msg_len bytes at msg_stride on the device and writes n uint32 to d_group_of; it returns after the result is complete.
+ * Returns 0 or < 0.
+ *
+ * bgls_verify_aggregate_grouped returns 1 / 0 / < 0 exactly as bgls_verify_aggregate(curve, sig, keys, msg_blob, msg_off, n,
+ * allow_duplicates = 1) does.  n_groups: NULL or the number of distinct messages.  gt_out: NULL or the GT element
+ * e(-sig, g2) * prod e(H(m), sum of that message's keys) after the final exponentiation.
+ *   Keys in G2, signature in G1: Points constructed through bgls_check_points and its kin.  For such inputs the verdict AND the GT bytes
+ *     equal those of the ungrouped product over all n pairs.  Canonical encoding and curve membership of every key are checked as
+ *     everywhere else; for on-curve points outside the subgroups the verdict is unspecified (the call still does not fault).
+ *   Key sum at infinity: a group whose keys sum to the point at infinity contributes the factor 1.
+ *   n == 0: returns what bgls_verify_aggregate returns for n = 0 (1 iff sig is the point at infinity), and *n_groups = 0.
+ *   Whole-call errors are the sibling's: BGLS_ERR_ENCODING, BGLS_ERR_HASH, and BGLS_ERR_NO_DEVICE without a device (no CPU fallback).
+ *   BGLS_ERR_ARG, returned before any device work: non-monotone offsets, NULL arrays with n > 0, n at or above 2^30, and in the
+ *     _dev forms a msg_stride below msg_len.
+ *   There is no duplicate rule: this is the Kosk / distinct-message callers' mode.
+ * Grouping is by exact bytes: messages that differ in one byte or in length are different messages. */
+int bgls_group_messages(const uint8_t* msg_blob, const uint64_t* msg_off, size_t n, uint32_t* group_of, size_t* n_groups);
+int bgls_group_messages_dev(const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n, void* d_group_of, size_t* n_groups,
+                            void* stream);
+int bgls_verify_aggregate_grouped(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob,
+                                  const uint64_t* msg_off, size_t n, size_t* n_groups, uint8_t* gt_out);
+int bgls_verify_aggregate_grouped_dev(int curve, const void* d_sig, const void* d_keys, const void* d_msgs, size_t msg_len,
+                                      size_t msg_stride, size_t n, size_t* n_groups, uint8_t* gt_out, void* stream);
+
 /* ---- distinct messages (bgls/blsDistinctMessage.go) and key registration (bgls/blsKosk.go:44-69) ----------------------------------
  * The message that is hashed is derived from the signer's key: key i's uncompressed wire bytes followed by message i
  * (BGLS_KEYED_PREFIX: append(keys[i].MarshalUncompressed(), msgs[i]...), blsDistinctMessage.go:51; the key bytes go in verbatim, as the

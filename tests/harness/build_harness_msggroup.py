@@ -1,0 +1,30 @@
+"""Builds tests/harness/libhost_harness_msggroup.so (TEST-ONLY: the work plan of the indexed key sum and the message hash, msggroup.hpp, compiled
+for the host: msggroup_host.cpp).  Used by tests/test_msggroup_host.py, which builds it on first use."""
+import os, subprocess
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+CLANGXX = "/opt/rocm/lib/llvm/bin/clang++"
+SRC = os.path.join(HERE, "msggroup_host.cpp")
+SO = os.path.join(HERE, "libhost_harness_msggroup.so")
+
+
+def deps():
+    return [SRC, os.path.join(ROOT, "bgls_amd", "csrc", "msggroup.hpp")]
+
+
+def stale():
+    return not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps())
+
+
+def build(force=False, timeout=300):
+    if not force and not stale():
+        return SO
+    tmp = SO + ".tmp%d" % os.getpid()
+    subprocess.run([CLANGXX, "-std=c++17", "-O1", "-fPIC", "-shared", SRC, "-o", tmp], check=True, timeout=timeout)
+    os.replace(tmp, SO)
+    return SO
+
+
+if __name__ == "__main__":
+    print(build(force=True))
