@@ -96,6 +96,9 @@ SIGNATURES = {
     "bgls_verify_multi_subsets_h": (ci, [ctypes.c_uint64, u8p, u8p, sz, sz, u8p, u64p, u8p, u8p, u8p]),
     "bgls_verify_multi_subsets_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, sz, vp, sz, sz, u8p, u8p, u8p, vp]),
     "bgls_set_subset_complement": (ci, [ci]),
+    "bgls_verify_aggregate_grouped_h": (ci, [ctypes.c_uint64, u8p, u8p, sz, u8p, u64p, sz, ctypes.POINTER(sz), u8p]),
+    "bgls_verify_aggregate_grouped_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, vp, sz, sz, sz, ctypes.POINTER(sz), u8p, vp]),
+    "bgls_set_group_small": (ci, [sz]),
     "bgls_rccl_available": (ci, []),
     "bgls_verify_aggregate_h_gt": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, ci, u8p]),
     "bgls_generator": (ci, [ci, ci, u8p]),

@@ -121,10 +121,11 @@ def VerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):
     """KoskVerifyAggregateSignature's body (verifyAggSig with allowDuplicates = true, bgls/blsKosk.go:100-106) with one hash and one
     pairing per DISTINCT message: the keys of the signers of one message are summed first (bgls_verify_aggregate_grouped).  Same verdict
     as _verify_agg(..., True); messages are grouped by exact bytes; there is no duplicate rule.  keys: a list of G2 Points -- for a
-    resident KeySet use the signer-bitmap calls (VerifyMultiSignaturesBySubset, AggregateKeysBySubset)."""
+    resident KeySet use VerifyAggregateSignatureGroupedBySubset (or, for one message per set, the signer-bitmap calls
+    VerifyMultiSignaturesBySubset, AggregateKeysBySubset)."""
     if isinstance(keys, KeySet):
-        raise TypeError("VerifyAggregateSignatureGrouped takes a list of keys; over a KeySet use the signer-bitmap calls "
-                        "(VerifyMultiSignaturesBySubset / AggregateKeysBySubset)")
+        raise TypeError("VerifyAggregateSignatureGrouped takes a list of keys; over a KeySet use VerifyAggregateSignatureGroupedBySubset "
+                        "(or the signer-bitmap calls VerifyMultiSignaturesBySubset / AggregateKeysBySubset)")
     if len(keys) != len(msgs):                       # bgls/bgls.go:95-97
         return False
     if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
@@ -140,6 +141,41 @@ def VerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):
 
 def KoskVerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:100-106
     return VerifyAggregateSignatureGrouped(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs])
+
+
+def VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, msgs):
+    """VerifyAggregateSignatureGrouped whose keys are a sub-slice of a resident KeySet (bgls_verify_aggregate_grouped_h): nothing of a key
+    travels.  subset: None (every key; msgs[i] belongs to key i), a bytes bitmap (key i selected iff (bitmap[i >> 3] >> (i & 7)) & 1; msgs in
+    ascending key order) or a list of key indices, msgs parallel to the list as given -- a repeated index is a ValueError.  Every failure
+    of the call collapses to False (bgls.go:115-118)."""
+    if not isinstance(keyset, KeySet):
+        raise TypeError("VerifyAggregateSignatureGroupedBySubset takes a KeySet")
+    n = len(keyset)
+    ms = [bytes(m) for m in msgs]
+    if subset is None:
+        bitmap = None
+    elif isinstance(subset, (bytes, bytearray, memoryview)):
+        bitmap = bytes(subset)
+    else:
+        idx = [int(i) for i in subset]
+        if len(set(idx)) != len(idx):
+            raise ValueError("a key index is repeated in the subset")
+        if any(not 0 <= i < n for i in idx):
+            raise ValueError("a key index lies outside the key set")
+        if len(idx) != len(ms):                      # bgls/bgls.go:95-97
+            return False
+        order = sorted(range(len(idx)), key=lambda j: idx[j])
+        ms = [ms[j] for j in order]
+        bitmap = _subset_rows(keyset, [idx])[0]
+    if keyset.curve is not curve or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+        return False
+    rc = _lib.load().bgls_verify_aggregate_grouped_h(keyset.handle, _lib.buf(aggsig.raw), None if bitmap is None else _lib.buf(bitmap),
+                                                     0 if bitmap is None else len(bitmap), _lib.buf(b"".join(ms)), _offsets(ms), len(ms), None, None)
+    return rc == 1
+
+
+def KoskVerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, msgs):  # bgls/blsKosk.go:100-106
+    return VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, [b"\x01" + bytes(m) for m in msgs])
 
 
 def _verify_agg_batch(curve, aggsigs, keys_per_instance, msgs_per_instance, allow_duplicates):

@@ -633,6 +633,55 @@ int bgls_set_subset_complement(int mode) try {
   return 0;
 } BGLS_ABI_GUARD
 
+// Grouped aggregate verification over a one-device key set by signer bitmap.  The refusals come in the order of the subset calls: the
+// arguments alone, the machine, the handle, then (host form) the row against the handle's n.
+static int grouped_keys_keyset(bgls_keys_t handle, std::shared_ptr<KeySet>* ks) {
+  int rc;
+  if ((rc = subsets_no_device())) return rc;
+  if (!(*ks = keyset(handle))) return fail(BGLS_ERR_ARG, "unknown key-set handle");
+  return grouped_keys_args_ok(**ks);
+}
+
+int bgls_verify_aggregate_grouped_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* bitmap, size_t bitmap_len, const uint8_t* msg_blob,
+                                    const uint64_t* msg_off, size_t n_msgs, size_t* n_groups, uint8_t* gt_out) try {
+  if (n_msgs >= MAX_BATCH) return too_large();
+  if (!sig || !msg_off) return fail(BGLS_ERR_ARG, "NULL argument");
+  int rc;
+  if ((rc = offsets_ok("msg_off", msg_off, n_msgs, 0))) return rc;
+  if (msg_off[n_msgs] > msg_off[0] && !msg_blob) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n_groups) *n_groups = 0;
+  std::shared_ptr<KeySet> ks;
+  if ((rc = grouped_keys_keyset(handle, &ks))) return rc;
+  size_t selected = ks->n;
+  if (bitmap) {
+    if (bitmap_len < (ks->n + 7) / 8) return fail(BGLS_ERR_ARG, "the signer bitmap is shorter than ceil(n / 8) bytes");
+    if (!subset_rows_clean(bitmap, bitmap_len, 1, ks->n)) return fail(BGLS_ERR_ARG, "a signer bitmap has a bit at a position beyond the key set");
+    selected = subset_row_popcount(bitmap, ks->n);
+  }
+  if (selected != n_msgs) return fail(BGLS_ERR_ARG, "the signer bitmap does not select as many keys as there are messages");
+  DISPATCH(ks->curve, verify_aggregate_grouped_keys_t<CV>(*ks, sig, bitmap, msg_blob, msg_off, n_msgs, n_groups, gt_out));
+} BGLS_ABI_GUARD
+
+int bgls_verify_aggregate_grouped_keys_dev(bgls_keys_t handle, const void* d_sig, const void* d_bitmap, size_t bitmap_len, const void* d_msgs,
+                                           size_t msg_len, size_t msg_stride, size_t n_msgs, size_t* n_groups, uint8_t* gt_out, void* stream) try {
+  if (n_msgs >= MAX_BATCH) return too_large();
+  if (!d_sig || (n_msgs && !d_msgs)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (msg_stride < msg_len) return fail(BGLS_ERR_ARG, "msg_stride below msg_len");
+  if (d_bitmap && ((bitmap_len & 3) || ((uintptr_t)d_bitmap & 3)))
+    return fail(BGLS_ERR_ARG, "device bitmap: the length and the pointer must be multiples of 4 bytes");
+  if (n_groups) *n_groups = 0;
+  std::shared_ptr<KeySet> ks;
+  int rc;
+  if ((rc = grouped_keys_keyset(handle, &ks))) return rc;
+  if (d_bitmap && bitmap_len < 4 * ((ks->n + 31) / 32)) return fail(BGLS_ERR_ARG, "the device signer bitmap is shorter than 4 ceil(n / 32) bytes");
+  DISPATCH(ks->curve, verify_aggregate_grouped_keys_dev_t<CV>(*ks, d_sig, d_bitmap, bitmap_len, d_msgs, msg_len, msg_stride, n_msgs, n_groups, gt_out, stream));
+} BGLS_ABI_GUARD
+
+int bgls_set_group_small(size_t keys) try {
+  g_group_small.store(keys);
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_verify_aggregate_multi(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                                 size_t n, int allow_duplicates, const int* devices, int n_devices) try {
   if (n >= MAX_BATCH) return too_large();

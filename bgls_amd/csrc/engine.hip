@@ -41,6 +41,7 @@ typedef enum { ncclInt8 = 0, ncclUint8 = 1 } ncclDataType_t;
 #include "launch_tail.hpp"
 #include "sumsel.hpp"
 #include "msggroup.hpp"
+#include "grpkeys.hpp"
 #include "../../include/bgls_hip.h"
 
 using namespace bgls;

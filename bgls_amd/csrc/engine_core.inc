@@ -437,7 +437,9 @@ struct Engine {
     const uint64_t* item_start = nullptr;
     MsgView reps = {nullptr, nullptr, 0, 0};
   };
-  static int group_messages(Ctx& c, hipStream_t st, MsgView mv, size_t msg_bytes, size_t n, uint32_t* d_group_of, bool plan, Groups* out) {
+  // small (grpkeys.hpp): groups of at most that many keys get no work item -- their sums come from k_sumpairgrp_main (sum_groups); 0, what
+  // every caller but the key-set form passes, is the plan of msggroup.hpp.
+  static int group_messages(Ctx& c, hipStream_t st, MsgView mv, size_t msg_bytes, size_t n, uint32_t* d_group_of, bool plan, Groups* out, uint32_t small = 0) {
     if (n >= MAX_BATCH) return too_large();
     if (c.res_pending) return in_flight();                  // the pinned result words carry d and the item count to the host
     size_t cap = 2;
@@ -484,7 +486,7 @@ struct Engine {
     HIPCHK(hipMemsetAsync(u + o_cursor, 0, d * 4, st));
     HIPCHK(hipMemsetAsync(u + o_meta, 0, 8 * 4, st));
     kl::grp_scatter(st, n, group_of, u + o_start, u + o_cursor, u + o_idx);
-    kl::grp_nitems(st, d, u + o_start, chunk, u + o_nitems, u + o_meta);
+    kl::grp_nitems(st, d, u + o_start, chunk, small, u + o_nitems, u + o_meta);
     kl::scan_excl<uint32_t, uint64_t>(st, u + o_nitems, d, v + o_bsum64, v + o_istart);
     kl::grp_items(st, d, u + o_start, v + o_istart, chunk, u + o_items, u + o_joins, u + o_multi, u + o_meta);
     HIPCHK(hipMemcpyAsync(&c.h_res[8], u + o_meta, 8, hipMemcpyDeviceToHost, st));
@@ -503,7 +505,7 @@ struct Engine {
     uint64_t n_items;
     memcpy(&n_items, &c.h_res[6], 8);
     const size_t largest = c.h_res[8], n_multi = c.h_res[9];
-    if (n_items < d || n_items > msggroup_max_items(n, d, chunk) || largest == 0 || largest > n || n_multi >= most_multi || (n_multi != 0) != (largest > chunk))
+    if ((small == 0 && n_items < d) || n_items > grpkeys_max_items(n, d, chunk, small) || largest == 0 || largest > n || n_multi >= most_multi || (n_multi != 0) != (largest > chunk))
       return fail(BGLS_ERR_HIP, "message grouping: inconsistent work plan");
     out->n_items = (size_t)n_items;
     out->n_multi = n_multi;
@@ -521,21 +523,31 @@ struct Engine {
   // else the sum of its partials (contiguous by construction) from a second pass of the same kernel, one block per such group, over the
   // partials' wire bytes.  There are fewer than n / chunk + 1 such groups.  A bad key anywhere sets FLAG_ENC.
   // Layout of WS_SEG_KEYS: d + 1 key sums | n_items partials | n_multi joined sums; WS_JAC_A: n_items partials, WS_JAC_B: n_multi.
-  static int sum_groups(Ctx& c, hipStream_t st, const uint8_t* d_keys, const Groups& g, const uint8_t** d_sums, uint32_t* d_flags) {
+  // recs = true (bgls_verify_aggregate_grouped_h): d_keys are a key set's sum-ready records, g.idx holds ranks among the selected keys sel
+  // (nullptr: every key, the ranks are the keys), and the plan was made with the threshold `small` -- the groups it left without an item
+  // are summed by one lane pair each (k_sumpairgrp_main: d Jacobian sums behind the partials in WS_JAC_A, infinity where a group has
+  // items), and k_jac_to_bytes puts all d of them in place before k_grp_pick / k_grp_place overwrite those of the groups with items.
+  static int sum_groups(Ctx& c, hipStream_t st, const uint8_t* d_keys, const Groups& g, const uint8_t** d_sums, uint32_t* d_flags, bool recs = false,
+                        const uint32_t* sel = nullptr, uint32_t small = 0) {
     const size_t JB = kl::jac_bytes<C>(BGLS_G2);
     if (g.n_items > ((size_t)1 << 30)) return fail(BGLS_ERR_ARG, "too many work items for one call");
     void *ja, *jb, *ks;
     int rc;
     Scope sc(c, st, ST_SUM);
-    if ((rc = c.get(WS_JAC_A, (g.n_items + 1) * JB, &ja))) return rc;
+    if ((rc = c.get(WS_JAC_A, (g.n_items + 1 + (small ? g.d : 0)) * JB, &ja))) return rc;
     if ((rc = c.get(WS_JAC_B, (g.n_multi + 1) * JB, &jb))) return rc;
     if ((rc = c.get(WS_SEG_KEYS, (g.d + 1 + g.n_items + g.n_multi) * G2B, &ks))) return rc;
     uint8_t *sums = (uint8_t*)ks, *parts = sums + (g.d + 1) * G2B, *joined = parts + g.n_items * G2B;
     {
       Scope scm(c, st, ST_SUM_MAIN);
-      kl::sumpairidx_main<C>(st, d_keys, g.idx, g.items, g.n_items, ja, d_flags);
+      if (!recs) kl::sumpairidx_main<C>(st, d_keys, g.idx, g.items, g.n_items, ja, d_flags);
+      else {
+        if (g.n_items) kl::sumpairidx_recs<C>(st, d_keys, g.idx, sel, g.items, g.n_items, ja, d_flags);
+        if (small) kl::sumpairgrp_main<C>(st, d_keys, g.idx, sel, g.start, g.d, small, (uint8_t*)ja + g.n_items * JB);
+      }
     }
-    kl::jac_to_bytes<C>(st, BGLS_G2, ja, g.n_items, parts);
+    if (small) kl::jac_to_bytes<C>(st, BGLS_G2, (uint8_t*)ja + g.n_items * JB, g.d, sums);
+    if (g.n_items) kl::jac_to_bytes<C>(st, BGLS_G2, ja, g.n_items, parts);
     kl::grp_pick(st, g.d, g.item_start, parts, G2B, sums);
     if (g.n_multi) {
       kl::sumpairidx_main<C>(st, parts, nullptr, g.joins, g.n_multi, jb, d_flags);

@@ -578,6 +578,123 @@ int verify_multi_subsets_dev_t(KeySet& ks, const void* d_sigs, const void* d_bit
   });
 }
 
+// ---- grouped aggregate verification over a one-shard key set by signer bitmap (bgls_verify_aggregate_grouped_h / _keys_dev) ----
+// bgls_set_group_small: groups of at most min(k, 128) keys are summed by one lane pair each (k_sumpairgrp_main); 0 = none.  The results do
+// not depend on it.  Default 32, by measurement (DESIGN.md section 6): at groups of 1, 4 and 16 keys every threshold from 32 up runs the
+// same kernels, at groups of 128 the serial chain of one lane pair loses to the block pass by 2x.
+std::atomic<size_t> g_group_small{32};
+
+// what the handle must be: a one-shard set, and the lane-pair key sum (the only reader of sum-ready records)
+int grouped_keys_args_ok(const KeySet& ks) {
+  if (ks.shards.size() != 1) return fail(BGLS_ERR_ARG, "grouped verification over a key set: the key set must live on one device");
+  if (!sum_pairs()) return fail(BGLS_ERR_ARG, "grouped verification over a key set: needs the lane-pair key sum (BGLS_LEGACY bit 8 is set)");
+  return 0;
+}
+
+// selected keys of a host row over n keys (its bytes below ceil(n / 8); the positions >= n are checked by subset_rows_clean)
+size_t subset_row_popcount(const uint8_t* row, size_t n) {
+  size_t k = 0;
+  for (size_t i = 0; i < (n + 7) / 8; ++i) k += (size_t)__builtin_popcount(row[i]);
+  return k;
+}
+
+// The selection pass (grpkeys.hpp; under ST_GROUP), the grouping of the k = n_msgs messages with the small / large plan, the key sums of
+// the d groups from the set's sum-ready records -- key sel[idx[p]], or idx[p] where everybody signs (d_row == nullptr) -- and the
+// sibling's tail: the product over the d (key sum, representative message) pairs and ONE final exponentiation.
+// d_row: row_words 32-bit words, of which the first grpkeys_words(n) hold the keys; a bit at a position >= n or a popcount other than
+// n_msgs fails the call here, whatever the host checked before.  The selection lives in WS_AMS_SIGNERS, which nothing else in this call
+// touches: sel (n_msgs) | cnt (words) | rank (words + 1) | the scan's block sums; all of it is written before it is read.
+template <class C>
+int verify_aggregate_grouped_keys_run(Ctx& c, hipStream_t st, const KeySet& ks, const uint8_t* d_sig, const uint32_t* d_row, size_t row_words, MsgView mv,
+                                      size_t msg_bytes, size_t n_msgs, size_t* n_groups, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  if (c.res_pending) return in_flight();
+  int rc;
+  void *d_flags, *d_part, *d_none;
+  if ((rc = c.get(WS_FLAGS, 16, &d_flags))) return rc;
+  if ((rc = c.get(WS_PART, E::GTB, &d_part))) return rc;
+  HIPCHK(hipMemsetAsync(d_flags, 0, 4, st));
+  const uint32_t* sel = nullptr;
+  if (d_row) {
+    const size_t nw = grpkeys_words(ks.n), tiles = kl::scan_tiles(nw + 1);
+    size_t w32 = 0;
+    auto take = [](size_t& at, size_t words) { const size_t r = at; at += (words + 63) & ~(size_t)63; return r; };
+    const size_t o_sel = take(w32, n_msgs), o_cnt = take(w32, nw), o_rank = take(w32, nw + 1), o_bsum = take(w32, tiles + 1);
+    void* arena;
+    if ((rc = c.get(WS_AMS_SIGNERS, w32 * 4, &arena))) return rc;
+    uint32_t* u = (uint32_t*)arena;
+    c.h_res[10] = c.h_res[11] = 0;
+    {
+      Scope sc(c, st, ST_GROUP);
+      if (row_words) kl::sel_count(st, d_row, row_words, ks.n, u + o_cnt, (uint32_t*)d_flags);
+      if (nw) {
+        kl::scan_excl<uint32_t, uint32_t>(st, u + o_cnt, nw, u + o_bsum, u + o_rank);
+        kl::sel_scatter(st, d_row, ks.n, u + o_rank, (uint32_t)n_msgs, u + o_sel);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    if (nw) HIPCHK(hipMemcpyAsync(&c.h_res[10], u + o_rank + nw, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&c.h_res[11], d_flags, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (c.h_res[11] & FLAG_SUBSET_STRAY) return fail(BGLS_ERR_ARG, "a signer bitmap has a bit at a position beyond the key set");
+    if (c.h_res[10] != n_msgs) return fail(BGLS_ERR_ARG, "the signer bitmap does not select as many keys as there are messages");
+    sel = u + o_sel;
+  } else if (n_msgs != ks.n) {
+    return fail(BGLS_ERR_ARG, "message count differs from the key set's size");
+  }
+  typename E::Groups g;
+  if ((rc = c.get(WS_SEG_KEYS, 16, &d_none))) return rc;
+  const uint8_t* d_sums = (const uint8_t*)d_none;                // no signer: nothing of it is read
+  if (n_msgs) {
+    const uint32_t small = grpkeys_small(g_group_small.load());
+    if ((rc = E::group_messages(c, st, mv, msg_bytes, n_msgs, nullptr, true, &g, small))) return rc;
+    if ((rc = E::sum_groups(c, st, (const uint8_t*)ks.shards[0].d_sumr, g, &d_sums, (uint32_t*)d_flags, true, sel, small))) return rc;
+    mv = g.reps;
+  }
+  if ((rc = E::miller_product(c, st, d_sig, d_sums, mv, g.d, 0, (uint8_t*)d_part, (uint32_t*)d_flags))) return rc;
+  if (n_groups) *n_groups = g.d;
+  return E::finalize(c, st, (const uint8_t*)d_part, 1, 1, (const uint32_t*)d_flags, gt_out);
+}
+
+// host form: the row (checked by the caller: no stray bit, popcount = n_msgs) repacked to whole 32-bit words and staged in WS_IN_B
+template <class C>
+int verify_aggregate_grouped_keys_t(KeySet& ks, const uint8_t* sig, const uint8_t* bitmap, const uint8_t* blob, const uint64_t* off, size_t n_msgs,
+                                    size_t* n_groups, uint8_t* gt_out) {
+  typedef Engine<C> E;
+  SelectionGuard keep_selection;
+  g_dev = ks.shards[0].device;
+  Call k;
+  if (k.rc) return k.rc;
+  Ctx& c = k.c;
+  int rc;
+  MsgView mv;
+  void *d_sig, *d_row = nullptr;
+  const size_t nw = grpkeys_words(ks.n);
+  std::vector<uint32_t> packed;                             // the source of an asynchronous copy: alive until the stream is drained
+  Drain drain{k.st};
+  if ((rc = upload_msgs(c, k.st, blob, off, n_msgs, &mv))) return rc;
+  if ((rc = c.put(k.st, WS_IN_A, sig, E::G1B, &d_sig))) return rc;
+  if (bitmap) {
+    packed.assign(nw, 0u);
+    if (nw) memcpy(packed.data(), bitmap, (ks.n + 7) / 8);
+    if ((rc = c.put(k.st, WS_IN_B, packed.data(), nw * 4, &d_row))) return rc;
+  }
+  return verify_aggregate_grouped_keys_run<C>(c, k.st, ks, (const uint8_t*)d_sig, (const uint32_t*)d_row, nw, mv, n_msgs ? off[n_msgs] : 0, n_msgs, n_groups,
+                                              gt_out);
+}
+
+template <class C>
+int verify_aggregate_grouped_keys_dev_t(KeySet& ks, const void* d_sig, const void* d_bitmap, size_t bitmap_len, const void* d_msgs, size_t msg_len,
+                                        size_t msg_stride, size_t n_msgs, size_t* n_groups, uint8_t* gt_out, void* stream) {
+  SelectionGuard keep_selection;
+  g_dev = ks.shards[0].device;
+  Call k(stream);
+  if (k.rc) return k.rc;
+  const MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
+  return verify_aggregate_grouped_keys_run<C>(k.c, k.st, ks, (const uint8_t*)d_sig, (const uint32_t*)d_bitmap, bitmap_len / 4, mv, n_msgs * msg_len, n_msgs,
+                                              n_groups, gt_out);
+}
+
 bool group_ok(int g) { return g == BGLS_G1 || g == BGLS_G2; }
 
 }  // namespace

@@ -14,6 +14,11 @@
 //   k_grp_nitems, scan, k_grp_items      the work items {lo, hi} of every group, item_start[g] .. item_start[g + 1], and the join list: the
 //                   groups of several items, one work item of the second pass each (their partials, contiguous by construction)
 //   k_grp_lens, scan, k_grp_compact      the representatives' bytes, contiguous, behind d + 1 offsets (or at the fixed stride of the input)
+// In front of all that, for bgls_verify_aggregate_grouped_h / _keys_dev (signers selected from a key set by ONE bitmap row; grpkeys.hpp):
+//   k_sel_count, scan, k_sel_scatter     sel[0 .. k) = the selected key indices, ascending; a bit at a position >= n raises FLAG_SUBSET_STRAY.
+//                   The grouping then runs over the k messages as it is: idx holds ranks, the key of position p is sel[idx[p]].
+//                   With a threshold `small` the plan (k_grp_nitems) gives a group of at most that many keys no item: its sum is
+//                   k_sumpairgrp_main's (k_sumpair.hip).
 // After the key sum: k_grp_pick / k_grp_place put the partial of a one-item group and the joined sum of a several-item group in place.
 // Contention: with all n messages equal every record meets ONE slot, ONE counter and ONE cursor.  The table word is read before it is
 // CAS-ed (after the first insert everybody sees it taken), and the lanes of a wave that hold the same slot / group elect their lowest lane
@@ -22,6 +27,8 @@
 #include "dev_common.hpp"
 #include "launch.hpp"
 #include "msggroup.hpp"
+#include "grpkeys.hpp"
+#include "sumsel.hpp"
 
 using namespace bgls;
 
@@ -112,13 +119,13 @@ __global__ void __launch_bounds__(256) k_grp_scatter(size_t n, const uint32_t* g
   if (active) idx[start[g] + base + (uint32_t)__popcll(same & ((1ull << lane_id()) - 1ull))] = (uint32_t)i;
 }
 
-// items per group, and the largest group to meta[0] (one atomic per wave)
-__global__ void __launch_bounds__(256) k_grp_nitems(size_t d, const uint32_t* start, uint32_t chunk, uint32_t* nitems, uint32_t* meta) {
+// items per group (none for a group of at most `small` keys: grpkeys.hpp), and the largest group to meta[0] (one atomic per wave)
+__global__ void __launch_bounds__(256) k_grp_nitems(size_t d, const uint32_t* start, uint32_t chunk, uint32_t small, uint32_t* nitems, uint32_t* meta) {
   const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   uint32_t c = 0;
   if (g < d) {
     c = start[g + 1] - start[g];
-    nitems[g] = msggroup_items_of(c, chunk);
+    nitems[g] = grpkeys_items_of(c, chunk, small);
   }
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) {
@@ -136,7 +143,7 @@ __global__ void __launch_bounds__(256) k_grp_items(size_t d, const uint32_t* sta
   if (g >= d) return;
   const uint32_t s = start[g], c = start[g + 1] - s;
   const uint64_t at = item_start[g];
-  const uint32_t cnt = (uint32_t)(item_start[g + 1] - at);          // = msggroup_items_of(c, chunk)
+  const uint32_t cnt = (uint32_t)(item_start[g + 1] - at);          // = grpkeys_items_of(c, chunk, small): 0 for a small group
   for (uint32_t k = 0; k < cnt; ++k) {
     uint32_t lo, hi;
     msggroup_item(s, c, k, chunk, &lo, &hi);
@@ -164,6 +171,26 @@ __global__ void __launch_bounds__(256) k_grp_place(size_t m, const uint32_t* mul
   const size_t k = t / rec_words;
   const unsigned w = (unsigned)(t % rec_words);
   if (k < m) sums[(size_t)multi[k] * rec_words + w] = joined[k * rec_words + w];
+}
+
+// ---- selection pass of the grouped verification over a key set (grpkeys.hpp): one bitmap row -> the selected key indices, ascending.
+// k_sel_count: cnt[w] = popcount of word w below n, for the words that hold positions below n; every one of the row's row_words words
+// is looked at, and a bit at a position >= n raises FLAG_SUBSET_STRAY.  The exclusive scan of cnt gives the ranks and, behind them, k.
+// k_sel_scatter: word w names its positions at sel[rank[w] ..]; nothing at or beyond cap is written, whatever the row holds.
+__global__ void __launch_bounds__(256) k_sel_count(const uint32_t* row, size_t row_words, size_t n, uint32_t* cnt, uint32_t* flags) {
+  const size_t w = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  bool stray = false;
+  if (w < row_words) {
+    const uint32_t v = grpkeys_word(row[w], n, w, &stray);
+    if (w < grpkeys_words(n)) cnt[w] = (uint32_t)__popc(v);
+  }
+  if (__ballot(stray) != 0 && lane_id() == 0) atomicOr(flags, FLAG_SUBSET_STRAY);
+}
+__global__ void __launch_bounds__(256) k_sel_scatter(const uint32_t* row, size_t n, const uint32_t* rank, uint32_t cap, uint32_t* sel) {
+  const size_t w = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  if (w >= grpkeys_words(n)) return;
+  bool stray;
+  (void)grpkeys_scatter(grpkeys_word(row[w], n, w, &stray), w, rank[w], cap, sel);
 }
 
 __global__ void __launch_bounds__(256) k_grp_lens(MsgView mv, size_t d, const uint32_t* rep_idx, uint64_t* lens) {
@@ -284,8 +311,14 @@ void grp_groups(hipStream_t st, size_t n, const uint32_t* slot_of, const uint32_
 void grp_scatter(hipStream_t st, size_t n, const uint32_t* group_of, const uint32_t* start, uint32_t* cursor, uint32_t* idx) {
   k_grp_scatter<<<nblk(n, 256), 256, 0, st>>>(n, group_of, start, cursor, idx);
 }
-void grp_nitems(hipStream_t st, size_t d, const uint32_t* start, uint32_t chunk, uint32_t* nitems, uint32_t* meta) {
-  k_grp_nitems<<<nblk(d, 256), 256, 0, st>>>(d, start, chunk, nitems, meta);
+void grp_nitems(hipStream_t st, size_t d, const uint32_t* start, uint32_t chunk, uint32_t small, uint32_t* nitems, uint32_t* meta) {
+  k_grp_nitems<<<nblk(d, 256), 256, 0, st>>>(d, start, chunk, small, nitems, meta);
+}
+void sel_count(hipStream_t st, const uint32_t* row, size_t row_words, size_t n, uint32_t* cnt, uint32_t* flags) {
+  k_sel_count<<<nblk(row_words, 256), 256, 0, st>>>(row, row_words, n, cnt, flags);
+}
+void sel_scatter(hipStream_t st, const uint32_t* row, size_t n, const uint32_t* rank, uint32_t cap, uint32_t* sel) {
+  k_sel_scatter<<<nblk(grpkeys_words(n), 256), 256, 0, st>>>(row, n, rank, cap, sel);
 }
 void grp_items(hipStream_t st, size_t d, const uint32_t* start, const uint64_t* item_start, uint32_t chunk, void* items, void* joins, uint32_t* multi, uint32_t* meta) {
   k_grp_items<<<nblk(d, 256), 256, 0, st>>>(d, start, item_start, chunk, (uint2*)items, (uint2*)joins, multi, meta);

@@ -1,7 +1,9 @@
 // G2 key sums (the main pass of AggregatePoints, curves/curve.go:73-121) on LANE PAIRS in the carry-free form: rx_jacpair.hpp.
 //   k_sumpair_main      pair t adds keys t, t + T, t + 2T, ... (T = lane pairs in the launch) into its own Jacobian sum
 //   k_sumpairseg_main   the same for nsets key sets in one launch (KoskVerifyBatchMultiSignature, bgls/blsKosk.go:126-133)
-//   k_sumpairidx_main   the same over an index list cut into work items, one block each (bgls_verify_aggregate_grouped)
+//   k_sumpairidx_main   the same over an index list cut into work items, one block each (bgls_verify_aggregate_grouped; over a key
+//                       set's sum-ready records, by rank among the selected keys: bgls_verify_aggregate_grouped_h)
+//   k_sumpairgrp_main   one lane pair per SMALL group of that call: its whole run, serially, and none of the tree below
 // The 32 sums of a block (one wave) are then added in the block, five levels through LDS (general Jacobian additions shared by
 // the two lane pairs whose sums they join), so that a block leaves ONE partial: 3072 for 2^20 keys instead of 98 304, and the tree above them (k_sum_coop:
 // one wave per addition) starts where it has few enough additions to be worth a wave each.  Partials leave in the library's
@@ -12,6 +14,7 @@
 #include "rx_jacpair.hpp"
 #include "launch.hpp"
 #include "sumsel.hpp"
+#include "grpkeys.hpp"
 
 namespace bgls {
 
@@ -201,8 +204,11 @@ __global__ void __launch_bounds__(64, 3) k_sumpairseg_main(const uint8_t* pts, c
 // msggroup_chunk(n) of them, all of one group); lane pair t adds keys idx[lo + t], idx[lo + t + 32], ...  One partial per item, in item
 // order: the partials of a group are contiguous.  The time follows the number of keys, not the shape of the group sizes.  idx == nullptr:
 // the positions are the keys -- the second pass, whose "keys" are the wire bytes of a group's partials and whose items are whole groups.
-template <class C>
-__global__ void __launch_bounds__(64, 3) k_sumpairidx_main(const uint8_t* pts, const uint32_t* idx, const uint2* items, Jac<F2<C>>* out, uint32_t* flags) {
+// SRC = 2, over a key set's sum-ready records (bgls_verify_aggregate_grouped_h): nothing is parsed or checked.  SEL: idx holds RANKS among
+// the keys a signer bitmap selects, and the key is sel[idx[k]] (the selection pass, grpkeys.hpp); without it sel is not looked at.
+template <class C, int SRC, bool SEL>
+__global__ void __launch_bounds__(64, 3) k_sumpairidx_main(const uint8_t* pts, const uint32_t* idx, const uint32_t* sel, const uint2* items, Jac<F2<C>>* out,
+                                                           uint32_t* flags) {
   const uint2 it = items[blockIdx.x];
   const bool odd = threadIdx.x & 1;
   JacP<C> acc = jacp_inf<C>();
@@ -210,12 +216,44 @@ __global__ void __launch_bounds__(64, 3) k_sumpairidx_main(const uint8_t* pts, c
 #pragma unroll 1
   for (uint32_t k = it.x + (threadIdx.x >> 1); k < it.y; k += 32) {
     AffP<C> q;
-    bad = !sumpair_fetch<C, 0>(q, pts, idx ? idx[k] : k, odd) || bad;
+    uint32_t key = idx ? idx[k] : k;
+    if constexpr (SEL) key = sel[key];
+    bad = !sumpair_fetch<C, SRC>(q, pts, key, odd) || bad;
     acc = jacp_madd<C>(acc, q, odd);
   }
   if (bad && !odd) atomicOr(flags, FLAG_ENC);
   acc = sumpair_block_tree<C>(acc, odd);
   if (threadIdx.x < 2) sumpair_store<C>(out + blockIdx.x, acc, odd);
+}
+
+// The SMALL groups of the grouped verification over a key set (grpkeys.hpp): lane pair p of the launch owns group p and, where the group
+// has at most `small` keys, adds its whole run of the index list serially into one Jacobian sum, out[p] -- 32 groups per wave, no block
+// tree, no partials to join.  A larger group (summed by the block pass) leaves the point at infinity in its place, so that every out[p]
+// is written.  The pairs of a wave have different trip counts: the loop runs while any pair has a key left, and the addition is
+// predicated on the pair (both lanes of a pair share the group, so they are always together, as k_sumsel_main's are).
+template <class C, bool SEL>
+__global__ void __launch_bounds__(64, 3) k_sumpairgrp_main(const uint8_t* recs, const uint32_t* idx, const uint32_t* sel, const uint32_t* start, size_t d,
+                                                           uint32_t small, Jac<F2<C>>* out) {
+  const size_t g = (size_t)blockIdx.x * 32 + (threadIdx.x >> 1);
+  const bool odd = threadIdx.x & 1;
+  uint32_t lo = 0, cnt = 0;
+  if (g < d) {
+    lo = start[g];
+    cnt = start[g + 1] - lo;
+    if (!grpkeys_is_small(cnt, small)) cnt = 0;
+  }
+  JacP<C> acc = jacp_inf<C>();
+#pragma unroll 1
+  for (uint32_t j = 0; __ballot(j < cnt) != 0; ++j) {
+    if (j < cnt) {
+      uint32_t key = idx[lo + j];
+      if constexpr (SEL) key = sel[key];
+      AffP<C> q;
+      (void)sumpair_fetch<C, 2>(q, recs, key, odd);
+      acc = jacp_madd<C>(acc, q, odd);
+    }
+  }
+  if (g < d) sumpair_store<C>(out + g, acc, odd);
 }
 
 // ---- key sums by signer bitmap over a key set's sum-ready records (bgls_verify_multi_subsets_h, bgls_aggregate_subsets_h) ----
@@ -396,10 +434,28 @@ void sumpairseg_main(hipStream_t st, const uint8_t* pts, const uint64_t* off, si
 template <class C>
 void sumpairidx_main(hipStream_t st, const uint8_t* pts, const uint32_t* idx, const void* items, size_t n_items, void* out, uint32_t* flags) {
   typedef typename SumForm<C>::type X;
-  k_sumpairidx_main<X><<<(unsigned)n_items, 64, 0, st>>>(pts, idx, (const uint2*)items, (Jac<F2<X>>*)out, flags);
+  k_sumpairidx_main<X, 0, false><<<(unsigned)n_items, 64, 0, st>>>(pts, idx, nullptr, (const uint2*)items, (Jac<F2<X>>*)out, flags);
 }
 template void sumpairidx_main<BN254>(hipStream_t, const uint8_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
 template void sumpairidx_main<BLS381>(hipStream_t, const uint8_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
+// the same over a key set's sum-ready records; sel != nullptr: idx holds ranks, the key is sel[idx[k]]
+template <class C>
+void sumpairidx_recs(hipStream_t st, const uint8_t* recs, const uint32_t* idx, const uint32_t* sel, const void* items, size_t n_items, void* out, uint32_t* flags) {
+  typedef typename SumForm<C>::type X;
+  if (sel) k_sumpairidx_main<X, 2, true><<<(unsigned)n_items, 64, 0, st>>>(recs, idx, sel, (const uint2*)items, (Jac<F2<X>>*)out, flags);
+  else k_sumpairidx_main<X, 2, false><<<(unsigned)n_items, 64, 0, st>>>(recs, idx, nullptr, (const uint2*)items, (Jac<F2<X>>*)out, flags);
+}
+template void sumpairidx_recs<BN254>(hipStream_t, const uint8_t*, const uint32_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
+template void sumpairidx_recs<BLS381>(hipStream_t, const uint8_t*, const uint32_t*, const uint32_t*, const void*, size_t, void*, uint32_t*);
+// d Jacobian sums, one per group: the sum of a group of at most `small` keys, infinity for every other group (k_sumpairgrp_main)
+template <class C>
+void sumpairgrp_main(hipStream_t st, const uint8_t* recs, const uint32_t* idx, const uint32_t* sel, const uint32_t* start, size_t d, uint32_t small, void* out) {
+  typedef typename SumForm<C>::type X;
+  if (sel) k_sumpairgrp_main<X, true><<<nblk(d, 32), 64, 0, st>>>(recs, idx, sel, start, d, small, (Jac<F2<X>>*)out);
+  else k_sumpairgrp_main<X, false><<<nblk(d, 32), 64, 0, st>>>(recs, idx, nullptr, start, d, small, (Jac<F2<X>>*)out);
+}
+template void sumpairgrp_main<BN254>(hipStream_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, size_t, uint32_t, void*);
+template void sumpairgrp_main<BLS381>(hipStream_t, const uint8_t*, const uint32_t*, const uint32_t*, const uint32_t*, size_t, uint32_t, void*);
 void sumsel_plan(hipStream_t st, const uint32_t* rows, size_t stride_w, size_t n, size_t nsets, int mode, uint32_t* plan, uint32_t* flags) {
   k_sumsel_plan<<<(unsigned)nsets, 64, 0, st>>>(rows, stride_w, n, mode, plan, flags);
 }

@@ -29,7 +29,12 @@ void grp_mark(hipStream_t st, size_t n, const uint32_t* slot_of, const uint32_t*
 void grp_assign(hipStream_t st, size_t n, const uint32_t* rep, const uint32_t* rank, const uint32_t* slot_of, uint32_t* table, uint32_t* rep_idx);
 void grp_groups(hipStream_t st, size_t n, const uint32_t* slot_of, const uint32_t* table, uint32_t* group_of, uint32_t* count);
 void grp_scatter(hipStream_t st, size_t n, const uint32_t* group_of, const uint32_t* start, uint32_t* cursor, uint32_t* idx);
-void grp_nitems(hipStream_t st, size_t d, const uint32_t* start, uint32_t chunk, uint32_t* nitems, uint32_t* meta);      // meta[0] <- max(meta[0], largest group)
+// small: groups of at most that many keys get no item (grpkeys.hpp; 0: every group has items)
+void grp_nitems(hipStream_t st, size_t d, const uint32_t* start, uint32_t chunk, uint32_t small, uint32_t* nitems, uint32_t* meta);      // meta[0] <- max(meta[0], largest group)
+// selection pass (grpkeys.hpp): cnt[w] for the grpkeys_words(n) words below n, FLAG_SUBSET_STRAY for a bit >= n anywhere in row_words words;
+// then, behind the scan of cnt, sel[rank[w] ..] = the positions word w selects (nothing at or beyond cap)
+void sel_count(hipStream_t st, const uint32_t* row, size_t row_words, size_t n, uint32_t* cnt, uint32_t* flags);
+void sel_scatter(hipStream_t st, const uint32_t* row, size_t n, const uint32_t* rank, uint32_t cap, uint32_t* sel);
 // items: {lo, hi} per item; joins / multi: the meta[1] groups of several items, {first, last + 1} of their partials and the group (meta[1] from 0)
 void grp_items(hipStream_t st, size_t d, const uint32_t* start, const uint64_t* item_start, uint32_t chunk, void* items, void* joins, uint32_t* multi, uint32_t* meta);
 // key sums to their places (rec_bytes each, a multiple of 16): a one-item group's partial from parts[item_start[g]]; joined sum k to group multi[k]
@@ -49,6 +54,12 @@ template <class C> void sumpairseg_main(hipStream_t st, const uint8_t* pts, cons
 // items: n_items pairs {lo, hi} (uint2) of positions in the index list idx (nullptr: the positions themselves), one block and one Jacobian
 // partial per item (msggroup.hpp)
 template <class C> void sumpairidx_main(hipStream_t st, const uint8_t* pts, const uint32_t* idx, const void* items, size_t n_items, void* out, uint32_t* flags);
+// the same over a key set's sum-ready records (no parsing, no curve check); sel != nullptr: idx holds ranks among the keys a signer bitmap
+// selects, the key is sel[idx[k]] (grpkeys.hpp)
+template <class C> void sumpairidx_recs(hipStream_t st, const uint8_t* recs, const uint32_t* idx, const uint32_t* sel, const void* items, size_t n_items, void* out, uint32_t* flags);
+// d Jacobian sums, one per group and lane pair: the sum of a group of at most `small` keys (its run start[g] .. start[g + 1] of idx), the
+// point at infinity for every other group
+template <class C> void sumpairgrp_main(hipStream_t st, const uint8_t* recs, const uint32_t* idx, const uint32_t* sel, const uint32_t* start, size_t d, uint32_t small, void* out);
 template <class C> void sum_wave(hipStream_t st, int group, const void* in, size_t n, void* out);
 template <class C> void sum_pair(hipStream_t st, int group, const void* in, size_t n, void* out);
 template <class C> void sum_coop(hipStream_t st, const void* in, size_t n, void* out);        // G2, one wave per addition (jac_coop.hpp)

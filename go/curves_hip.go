@@ -451,6 +451,63 @@ func (ks *HipKeySet) HipVerifyMultiSubsets(aggsigs []Point, subsets [][]int, msg
 	return out
 }
 
+// HipVerifyAggregateGroupedBySubset is verifyAggSig with allowDuplicates = true (KoskVerifyAggregateSignature's body,
+// bgls/blsKosk.go:100-106) whose keys are the resident keys listed in subset, msgs[j] the message of key subset[j], with one hash and one
+// pairing per DISTINCT message: ONE bgls_verify_aggregate_grouped_h call.  subset == nil: every key, msgs[i] the message of key i.  The
+// call wants the messages in ascending key order: they are reordered here.  A repeated or foreign index, a length mismatch and every
+// failure of the call are false.  For KoskVerifyAggregateSignature the caller prepends 0x01 to every message.
+// Like the rest of this file this wrapper is text: it has never been compiled (no Go toolchain where the library is built).
+func (ks *HipKeySet) HipVerifyAggregateGroupedBySubset(aggsig Point, subset []int, msgs [][]byte) bool {
+	s, ok := aggsig.(*hipPoint)
+	if !ok || s.c != ks.c || s.group != C.BGLS_G1 {
+		return false
+	}
+	order := make([]int, 0, len(msgs))
+	var row []byte
+	if subset == nil {
+		if len(msgs) != ks.n {
+			return false
+		}
+		for j := range msgs {
+			order = append(order, j)
+		}
+	} else {
+		if len(subset) != len(msgs) {
+			return false
+		}
+		at := make([]int, ks.n)
+		for i := range at {
+			at[i] = -1
+		}
+		row = make([]byte, ks.n/8+1)
+		for j, i := range subset {
+			if i < 0 || i >= ks.n || at[i] >= 0 {
+				return false
+			}
+			at[i] = j
+			row[i>>3] |= 1 << uint(i&7)
+		}
+		for _, j := range at {
+			if j >= 0 {
+				order = append(order, j)
+			}
+		}
+	}
+	off := make([]C.uint64_t, len(msgs)+1)
+	var blob []byte
+	for k, j := range order {
+		blob = append(blob, msgs[j]...)
+		off[k+1] = C.uint64_t(len(blob))
+	}
+	var rowp *C.uint8_t
+	if row != nil {
+		rowp = p(row)
+	}
+	rc := C.bgls_verify_aggregate_grouped_h(ks.h, p(s.raw), rowp, C.size_t(len(row)), p(append(blob, 0)), &off[0], C.size_t(len(msgs)), nil, nil)
+	runtime.KeepAlive(ks)
+	return rc == 1
+}
+
 // HipAggregateKeysBySubset is AggregateKeys (bgls/bgls.go:129-131) over every index list in ONE bgls_aggregate_subsets_h call; nil on an
 // index outside the set or a failed call.  Uncompiled text, as above.
 func (ks *HipKeySet) HipAggregateKeysBySubset(subsets [][]int) []Point {

@@ -227,6 +227,52 @@ class KeySet {
     }
     return VerifyMultiSignaturesBySubset(aggsigs, subsets, ms);
   }
+  // verifyAggSig with allowDuplicates = true (bgls/blsKosk.go:100-106) over the sub-slice `subset` of the resident keys, with one hash and
+  // one pairing per DISTINCT message (bgls_verify_aggregate_grouped_h): msgs[j] is the message of key subset[j], in the order given (the
+  // call wants ascending key order: reordered here).  all = true: every key, msgs[i] the message of key i, subset ignored.  A repeated
+  // or foreign index, a length mismatch and every failure of the call are false.
+  bool VerifyAggregateSignatureGroupedBySubset(const Point& aggsig, const std::vector<size_t>& subset, const std::vector<Bytes>& msgs,
+                                               size_t* n_groups = nullptr, bool all = false) const {
+    if (!ok_ || aggsig.curve != curve_ || aggsig.group != BGLS_G1) return false;
+    std::vector<size_t> order(msgs.size());
+    Bytes row;
+    if (all) {
+      if (msgs.size() != n_) return false;
+      for (size_t j = 0; j < order.size(); ++j) order[j] = j;
+    } else {
+      if (subset.size() != msgs.size()) return false;
+      std::vector<long long> at(n_, -1);
+      row.assign(stride(), 0);
+      for (size_t j = 0; j < subset.size(); ++j) {
+        if (subset[j] >= n_ || at[subset[j]] >= 0) return false;
+        at[subset[j]] = (long long)j;
+        row[subset[j] >> 3] |= (uint8_t)(1u << (subset[j] & 7));
+      }
+      size_t k = 0;
+      for (size_t i = 0; i < n_; ++i)
+        if (at[i] >= 0) order[k++] = (size_t)at[i];
+    }
+    Bytes blob;
+    std::vector<uint64_t> off(msgs.size() + 1, 0);
+    for (size_t j = 0; j < order.size(); ++j) {
+      blob.insert(blob.end(), msgs[order[j]].begin(), msgs[order[j]].end());
+      off[j + 1] = blob.size();
+    }
+    blob.push_back(0);                                     // never an empty array
+    return bgls_verify_aggregate_grouped_h(h_, aggsig.raw.data(), all ? nullptr : row.data(), row.size(), blob.data(), off.data(), msgs.size(), n_groups,
+                                           nullptr) == 1;
+  }
+  // the same for KoskVerifyAggregateSignature: 0x01 prepended to every message
+  bool KoskVerifyAggregateSignatureGroupedBySubset(const Point& aggsig, const std::vector<size_t>& subset, const std::vector<Bytes>& msgs,
+                                                   size_t* n_groups = nullptr, bool all = false) const {
+    std::vector<Bytes> ms;
+    for (const Bytes& m : msgs) {
+      Bytes p(1, 1);
+      p.insert(p.end(), m.begin(), m.end());
+      ms.push_back(p);
+    }
+    return VerifyAggregateSignatureGroupedBySubset(aggsig, subset, ms, n_groups, all);
+  }
 
  private:
   size_t stride() const { return n_ / 8 + 1; }             // at least ceil(n / 8), never 0

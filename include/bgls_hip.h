@@ -662,6 +662,34 @@ int bgls_verify_multi_subsets_keys_dev(bgls_keys_t handle, const void* d_sigs, c
 /* Which side of a row the subset key sums add: 0 = chosen per set (complement when 2 popcount > n; default), 1 = never the complement,
  * 2 = always.  Process-wide; results do not depend on it (A/B measurements and tests). */
 int bgls_set_subset_complement(int mode);
+/* GROUPED aggregate verification by SIGNER BITMAP against a ONE-device key set: verifyAggSig with allowDuplicates = true
+ * (KoskVerifyAggregateSignature, bgls/blsKosk.go:100-106) whose keys are the sub-slice of the registered keys that ONE bitmap selects, with
+ * one hash and one pairing per DISTINCT message (bgls_verify_aggregate_grouped's product).  Key i is selected iff
+ * (bitmap[i >> 3] >> (i & 7)) & 1, the bit rule of the subset calls; bitmap == NULL selects every key (bitmap_len is then ignored).  Message j
+ * belongs to the j-th selected key in ascending key index, and n_msgs must equal the number of selected keys.  Nothing of a key is
+ * uploaded, parsed or checked again: the key sums read the resident sum-ready records (a set uploaded with BGLS_KEYS_PREPARE gives the
+ * same bytes).
+ *   bgls_verify_aggregate_grouped_h         signature, bitmap and messages (blob + n_msgs + 1 offsets) on the host
+ *   bgls_verify_aggregate_grouped_keys_dev  all three on the device, messages of msg_len bytes at msg_stride, on the calling thread's context
+ *                                           and the given stream; the bitmap is read as 32-bit words: bitmap_len and d_bitmap multiples of 4
+ * Returns 1 / 0 / < 0 exactly as bgls_verify_aggregate_grouped does on the gathered keys and the same messages; *n_groups (nullable) is the
+ * number of distinct messages and gt_out (nullable) the GT element, byte-equal to that call's.  No signer (no bit set and n_msgs == 0, or
+ * an empty key set) returns 1 iff sig is the point at infinity, with *n_groups = 0.  There is no duplicate rule.
+ * BGLS_ERR_ARG, before any device work: NULL sig; NULL msg_off (host form, also for n_msgs == 0); NULL msg_blob with bytes to read;
+ * non-monotone offsets; n_msgs at or above 2^30; device form: NULL d_msgs with n_msgs > 0, msg_stride < msg_len, d_bitmap or bitmap_len not a
+ * multiple of 4.  Then, without a device, BGLS_ERR_NO_DEVICE (before the handle is looked at).  Then BGLS_ERR_ARG again: an unknown
+ * handle; a key set on more than one device; the lane-pair key sum switched off (BGLS_LEGACY bit 8); bitmap_len < ceil(n / 8) (device
+ * form: < 4 ceil(n / 32)); a bit at a position >= n anywhere in bitmap_len; a popcount different from n_msgs -- the last two found on the
+ * host by the host form, by the selection pass of the device form, which then fails the whole call.  Whole-call errors are the
+ * sibling's: BGLS_ERR_ENCODING for a bad signature, BGLS_ERR_HASH. */
+int bgls_verify_aggregate_grouped_h(bgls_keys_t handle, const uint8_t* sig, const uint8_t* bitmap, size_t bitmap_len,
+                                    const uint8_t* msg_blob, const uint64_t* msg_off, size_t n_msgs, size_t* n_groups, uint8_t* gt_out);
+int bgls_verify_aggregate_grouped_keys_dev(bgls_keys_t handle, const void* d_sig, const void* d_bitmap, size_t bitmap_len,
+                                           const void* d_msgs, size_t msg_len, size_t msg_stride, size_t n_msgs, size_t* n_groups,
+                                           uint8_t* gt_out, void* stream);
+/* Groups of at most min(keys, 128) keys are summed by one lane pair each instead of a block (k_sumpairgrp_main); 0 switches that kernel
+ * off.  Default 32.  Process-wide; results never depend on it (A/B measurements and tests).  Returns 0, with or without a device. */
+int bgls_set_group_small(size_t keys);
 /* Contexts: a key-set verification runs shard s on context (selected + s) mod 16 of the shard's device, `selected` being the
  * calling thread's bgls_select_context (default 0); the final product / exponentiation runs on shard 0's context. */
 /* The same two calls with host keys, for callers without a resident set: upload (with BGLS_KEYS_CHECK: the keys have not been
