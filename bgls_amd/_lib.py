@@ -99,6 +99,7 @@ SIGNATURES = {
     "bgls_verify_aggregate_grouped_h": (ci, [ctypes.c_uint64, u8p, u8p, sz, u8p, u64p, sz, ctypes.POINTER(sz), u8p]),
     "bgls_verify_aggregate_grouped_keys_dev": (ci, [ctypes.c_uint64, vp, vp, sz, vp, sz, sz, sz, ctypes.POINTER(sz), u8p, vp]),
     "bgls_set_group_small": (ci, [sz]),
+    "bgls_set_prepare_shape": (ci, [sz, sz]),
     "bgls_rccl_available": (ci, []),
     "bgls_verify_aggregate_h_gt": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, ci, u8p]),
     "bgls_generator": (ci, [ci, ci, u8p]),

@@ -682,6 +682,15 @@ int bgls_set_group_small(size_t keys) try {
   return 0;
 } BGLS_ABI_GUARD
 
+int bgls_set_prepare_shape(size_t ng, size_t chunk) try {
+  if (ng != 0 && (ng < (size_t)PREP_NG_MIN || ng > (size_t)PREP_NG_MAX))
+    return fail(BGLS_ERR_ARG, "prepared shape: ng must be 0 (automatic) or lie in 6..96");
+  std::lock_guard<std::mutex> lk(g_prep_shape_mu);
+  g_prep_shape.ng = ng;
+  g_prep_shape.chunk = chunk;
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_verify_aggregate_multi(int curve, const uint8_t* sig, const uint8_t* keys, const uint8_t* msg_blob, const uint64_t* msg_off,
                                 size_t n, int allow_duplicates, const int* devices, int n_devices) try {
   if (n >= MAX_BATCH) return too_large();

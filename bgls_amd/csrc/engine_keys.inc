@@ -90,6 +90,13 @@ inline int prep_ng(size_t cnt) {
   if (ng > 96) ng = 96;                                                         // beyond 96 x 30 720 keys per device: several rounds
   return (int)ng;
 }
+// bgls_set_prepare_shape: NG forced for the key sets uploaded afterwards (0 = prep_ng) and the keys per k_prepare launch (0 = 2^17), packed
+// as {ng, chunk} so that an upload reads both from one setting.  The results do not depend on it (tests and A/B runs).
+constexpr int PREP_NG_MIN = 6, PREP_NG_MAX = 96;                                 // what prep_ng can return
+constexpr size_t PREP_CHUNK = (size_t)1 << 17;
+struct PrepShape { size_t ng = 0, chunk = 0; };
+std::mutex g_prep_shape_mu;
+PrepShape g_prep_shape;
 
 template <class C>
 int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* out) {
@@ -100,6 +107,11 @@ int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devic
   ks->n = n;
   ks->prepared = (flags & BGLS_KEYS_PREPARE) != 0;
   const size_t REC = E::GTB + REC_PAD;
+  PrepShape shape;                       // read once: every shard of this set is prepared under the same setting
+  {
+    std::lock_guard<std::mutex> lk(g_prep_shape_mu);
+    shape = g_prep_shape;
+  }
   bool distinct = true;
   for (int s = 0; s < n_devices; ++s) {
     KeyShard sh;
@@ -144,13 +156,13 @@ int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devic
       if (flags & BGLS_KEYS_PREPARE) {
         // line ratios of every key (k_prepare), in chunks so that the scratch stays a few GB
         const kl::PrepSizes ps = kl::prep_sizes<C>();
-        sh.ng = prep_ng<C>(cnt);
+        sh.ng = shape.ng ? (int)shape.ng : prep_ng<C>(cnt);
         const size_t pad = (size_t)10 * sh.ng;
         sh.n_pad = (cnt + pad - 1) / pad * pad;
         if (sh.n_pad == 0) sh.n_pad = pad;
         HIPCHK(hipMalloc(&sh.d_prep, sh.n_pad * ps.line_bytes_per_key));
         HIPCHK(hipMalloc(&sh.d_kinf, sh.n_pad));
-        const size_t chunk = (size_t)1 << 17;
+        const size_t chunk = shape.chunk ? shape.chunk : PREP_CHUNK;
         void* tmp = nullptr;
         HIPCHK(hipMalloc(&tmp, (sh.n_pad < chunk ? sh.n_pad : chunk) * ps.tmp_bytes_per_key));
         HIPCHK(hipMemsetAsync(d_flags, 0, 4, c.stream));

@@ -690,6 +690,10 @@ int bgls_verify_aggregate_grouped_keys_dev(bgls_keys_t handle, const void* d_sig
 /* Groups of at most min(keys, 128) keys are summed by one lane pair each instead of a block (k_sumpairgrp_main); 0 switches that kernel
  * off.  Default 32.  Process-wide; results never depend on it (A/B measurements and tests).  Returns 0, with or without a device. */
 int bgls_set_group_small(size_t keys);
+/* Shape of the key sets uploaded with BGLS_KEYS_PREPARE from now on: ng = pairings per group and squaring of the fold (0: chosen by the set's
+ * size; else 6..96), chunk = keys per preparation launch (0: 2^17).  A resident set keeps its shape.  Process-wide; results never depend on
+ * it (tests and A/B measurements).  Returns 0, or BGLS_ERR_ARG with the setting unchanged; with or without a device. */
+int bgls_set_prepare_shape(size_t ng, size_t chunk);
 /* Contexts: a key-set verification runs shard s on context (selected + s) mod 16 of the shard's device, `selected` being the
  * calling thread's bgls_select_context (default 0); the final product / exponentiation runs on shard 0's context. */
 /* The same two calls with host keys, for callers without a resident set: upload (with BGLS_KEYS_CHECK: the keys have not been

@@ -240,7 +240,8 @@ def test_rccl_is_loadable(gpu_lib):
 def test_prepared_key_set_gives_the_same_gt(gpu_lib, curve):
     """BGLS_KEYS_PREPARE: the Miller stage runs on the resident, normalised line functions of the keys (prepared.hpp).  Same
     verdicts and -- after the final exponentiation -- the same GT bytes as the unprepared set and the oracle, on one and on
-    several shards; keys at infinity and ragged sizes (padding up to whole fold groups) included."""
+    several shards; keys at infinity and ragged sizes (padding up to whole fold groups) included.  All of it at the automatic group
+    size 6: the other group sizes, the wave and chunk seams and degenerate keys are tests/test_gpu_prepared_shapes.py."""
     lib, cid, fp = gpu_lib, curve["id"], curve["fp"]
     for n, seed in ((5, 1), (333, 2), (1000, 3)):
         sks, keys, msgs, sigs, agg = make_instance(lib, cid, fp, n, 8800 + 10 * cid + seed)
