@@ -124,6 +124,7 @@ SIGNATURES = {
     "bgls_set_miller_shape": (ci, [ci, ci]),
     "bgls_weighted_sum_dev": (ci, [ci, ci, vp, vp, sz, vp, vp]),
     "bgls_set_msm_min": (ci, [sz]),
+    "bgls_set_msm_plan": (ci, [ci, ci]),
     "bgls_final_verify_dev": (ci, [ci, vp, sz, vp, vp]),
     "bgls_aggregate_points_dev": (ci, [ci, ci, vp, sz, vp, vp]),
     "bgls_verify_multi_dev": (ci, [ci, vp, vp, sz, vp, sz, vp]),
@@ -134,6 +135,7 @@ SIGNATURES = {
     "bgls_selftest_exception_barrier": (ci, [ci]),
     "bgls_selftest_fill_workspaces": (ci, [ci, ctypes.c_uint64, u64p]),
     "bgls_selftest_workspace_caps": (ci, [ctypes.POINTER(sz), ci]),
+    "bgls_selftest_msm_last": (ci, [u32p]),
 }
 
 _lib = None

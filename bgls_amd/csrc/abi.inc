@@ -955,6 +955,27 @@ int bgls_set_msm_min(size_t n) try {
   return 0;
 } BGLS_ABI_GUARD
 
+int bgls_set_msm_plan(int c, int S) try {
+  if (c != 0 && (c < 4 || c > 13)) return fail(BGLS_ERR_ARG, "bad window width (0 or 4..13)");
+  if (S != 0 && S != 1 && S != 2 && S != 4 && S != 8 && S != 16) return fail(BGLS_ERR_ARG, "bad threads per bucket (0, 1, 2, 4, 8 or 16)");
+  g_msm_plan.store(c << 8 | S);
+  return 0;
+} BGLS_ABI_GUARD
+
+// What the last weighted sum of the calling thread's context did (tests/test_gpu_msm_plans.py): out = {path, c, S, W, largest bucket,
+// listed pairs}; path 0 = per-point below bgls_set_msm_min's threshold (or past the 32-bit list guard), 1 = bucket method, 2 = per-point
+// after the histogram showed a bucket above max(8 (n >> c), 64).  All zero before the first sum; n == 0 leaves the report as it was.
+int bgls_selftest_msm_last(uint32_t* out) try {
+  if (!out) return fail(BGLS_ERR_ARG, "NULL argument");
+  int cnt = 0;
+  const hipError_t e0 = hipGetDeviceCount(&cnt);
+  if (e0 != hipSuccess || cnt <= 0) return fail(BGLS_ERR_NO_DEVICE, "no HIP device available", e0);
+  Ctx& c = ctx();
+  std::lock_guard<std::mutex> lk(c.mu);
+  for (int i = 0; i < 6; ++i) out[i] = c.msm_last[i];
+  return 0;
+} BGLS_ABI_GUARD
+
 int bgls_weighted_sum_dev(int curve, int group, const void* d_pts, const void* d_w16, size_t n, void* d_out, void* stream) try {
   if (group != BGLS_G1 && group != BGLS_G2) return fail(BGLS_ERR_ARG, "bad group");
   if (!d_out || (n && (!d_pts || !d_w16))) return fail(BGLS_ERR_ARG, "NULL argument");

@@ -123,6 +123,7 @@ struct Ctx {
   double stage_ms[16] = {0};
   unsigned long long stage_cnt[16] = {0};
   std::vector<uint64_t> stage_tab;           // host tables of a batch verification (offsets, reduce passes) on their way to WS_BATCH_IDX
+  uint32_t msm_last[6] = {0};                // what the last weighted sum did: path, c, S, W, largest bucket, listed pairs (bgls_selftest_msm_last)
   hipEvent_t ev() {
     if (!ev_pool.empty()) { hipEvent_t e = ev_pool.back(); ev_pool.pop_back(); return e; }
     hipEvent_t e = nullptr;

@@ -1268,6 +1268,8 @@ int hae_exponents_t(const uint8_t* keys, size_t n, uint8_t* t_out) {
 
 // Weighted sums below this many points keep one double-and-add per point (bgls_set_msm_min; tests pin both paths)
 std::atomic<size_t> g_msm_min{32};
+// bgls_set_msm_plan: window bits << 8 | threads per bucket forced on every weighted sum (0 = by size each); tests walk every plan with it
+std::atomic<int> g_msm_plan{0};
 
 // d_out (affine bytes) <- sum_i w_i P_i over device-resident points and 16-byte weights, one scalar multiplication per
 // point (k_wsum_first) followed by the addition tree
@@ -1300,6 +1302,9 @@ int weighted_sum_naive(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, 
 // The same sum by the bucket method (k_msm.hip): n W mixed additions instead of n (128 doublings + 64 additions).
 // Bucket populations are only balanced for weights that look random (hashed exponents do); when the largest bucket is
 // far above the mean -- small multiplicities, repeated weights -- the per-point form is the faster one and is used.
+// The top window holds only 128 - c (W - 1) bits (two at c = 6, 7 and 9; seven or eight at c = 11 and 12), so with uniform 128-bit
+// weights its buckets alone exceed the bound at the sizes that choose these widths, and such sums take the per-point form: measured
+// the faster one there (a thread per bucket walks the top window's long lists alone).
 template <class C>
 int weighted_sum_dev(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, const uint8_t* d_w16, const uint8_t* d_signs, size_t n,
                      uint8_t* d_out, uint32_t* d_flags) {
@@ -1310,7 +1315,10 @@ int weighted_sum_dev(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, co
   }
   if (n >= MAX_BATCH) return too_large();
   Scope sc(c, st, ST_SUM);
-  const kl::MsmPlan p = kl::msm_plan(n);
+  const int forced = g_msm_plan.load();
+  const kl::MsmPlan p = kl::msm_plan(n, forced >> 8, forced & 255);
+  uint32_t* last = c.msm_last;                                                          // path, c, S, W, largest bucket, listed pairs
+  last[0] = 0; last[1] = (uint32_t)p.c; last[2] = (uint32_t)p.S; last[3] = (uint32_t)p.W; last[4] = last[5] = 0;
   if (n < g_msm_min.load() || (uint64_t)n * (uint64_t)p.W >= (1ull << 32))            // list positions are 32-bit
     return weighted_sum_naive<C>(c, st, group, d_pts, d_w16, d_signs, n, d_out, d_flags);
   const size_t JB = kl::jac_bytes<C>(group);
@@ -1332,7 +1340,10 @@ int weighted_sum_dev(Ctx& c, hipStream_t st, int group, const uint8_t* d_pts, co
   HIPCHK(hipMemcpyAsync(meta, d_meta, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   const size_t mean = n >> p.c;
-  if (meta[0] > (mean * 8 > 64 ? mean * 8 : 64)) return weighted_sum_naive<C>(c, st, group, d_pts, d_w16, d_signs, n, d_out, d_flags);
+  last[4] = meta[0];
+  last[5] = meta[1];
+  last[0] = meta[0] > (mean * 8 > 64 ? mean * 8 : 64) ? 2 : 1;
+  if (last[0] == 2) return weighted_sum_naive<C>(c, st, group, d_pts, d_w16, d_signs, n, d_out, d_flags);
   void* res = nullptr;
   kl::msm_scatter<C>(st, group, aff, d_w16, n, p, (uint32_t*)cnt, (uint32_t*)list);
   kl::msm_buckets<C>(st, group, aff, (const uint32_t*)list, (const uint32_t*)start, p, buckets);

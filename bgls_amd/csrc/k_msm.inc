@@ -272,11 +272,13 @@ namespace kl {
 #if BGLS_UNIT_IS_BN
 // Window width: about eight points per bucket, between 4 and 13 bits (13: 10 windows x 8192 buckets = one thread per
 // bucket fills the chip; wider windows only add empty buckets at the batch sizes a uint32 XOF length allows).
-MsmPlan msm_plan(size_t n) {
+// force_c / force_s (bgls_set_msm_plan; 0 = by size): a test's window width and threads per bucket; W, NB, NQ and NCH follow c either way.
+MsmPlan msm_plan(size_t n, int force_c, int force_s) {
   int lg = 0;
   while (((size_t)2 << lg) <= n) ++lg;                  // floor(log2 n)
   int c = lg - 3;
   c = c < 4 ? 4 : c > 13 ? 13 : c;
+  if (force_c) c = force_c;
   MsmPlan p;
   p.c = c;
   p.W = (128 + c - 1) / c;
@@ -289,6 +291,7 @@ MsmPlan msm_plan(size_t n) {
   const size_t mean = n >> c;
   p.S = 1;
   while (p.S < 16 && (size_t)p.S * 2 * 8 <= mean) p.S *= 2;
+  if (force_s) p.S = force_s;
   return p;
 }
 #endif

@@ -84,7 +84,7 @@ template <class C> size_t jac_bytes(int group) { return (size_t)3 * (group == 1 
 
 // ---- k_msm.hip   (bucket-method weighted sums, fixed-base generator multiples, in-place G1 scaling)
 struct MsmPlan { int c, W, K, S; uint32_t NB, NQ, NCH; };    // window bits, windows, digits per chunk, threads per bucket, buckets, chunks per window, chunks
-MsmPlan msm_plan(size_t n);
+MsmPlan msm_plan(size_t n, int force_c = 0, int force_s = 0);      // force_*: bgls_set_msm_plan's override, 0 = chosen by n
 template <class C> size_t msm_aff_bytes(int group);
 template <class C>
 void msm_parse(hipStream_t st, int group, const uint8_t* pts, const uint8_t* w16, const uint8_t* signs, size_t n, const MsmPlan& p, void* aff,

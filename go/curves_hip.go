@@ -804,7 +804,8 @@ func HipAggregateSignaturesHAE(curve CurveSystem, sigs []Point, pubkeys []Point)
 }
 
 // HipVerifyMultiWithMultiplicity is the body of bgls.KoskVerifyMultiSignatureWithMultiplicity (bgls/blsKosk.go:137-150);
-// msg must already carry the Kosk 0x01 prefix.
+// msg must already carry the Kosk 0x01 prefix.  (The key sum's test knobs and report -- bgls_set_msm_min, bgls_set_msm_plan,
+// bgls_selftest_msm_last -- are left unbound on purpose: they change no result.)
 func HipVerifyMultiWithMultiplicity(curve CurveSystem, aggsig Point, keys []Point, multiplicity []int64, msg []byte) bool {
 	c, ok := curve.(*hipCurve)
 	s, ok2 := aggsig.(*hipPoint)

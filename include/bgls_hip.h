@@ -346,6 +346,11 @@ int bgls_set_ams_sum_cut(size_t n);
 int bgls_weighted_sum_dev(int curve, int group, const void* d_pts, const void* d_w16, size_t n, void* d_out, void* stream);
 /* Smallest n for which weighted sums take the bucket method (default 32; tests pin both paths with 0 / SIZE_MAX). */
 int bgls_set_msm_min(size_t n);
+/* Test-only, process-wide: the bucket method's window width c (4..13 bits; 0 = by size, clamp(floor(log2 n) - 3, 4, 13)) and its
+ * threads per bucket S (1, 2, 4, 8 or 16; 0 = by size) for every later weighted sum.  The windows ceil(128 / c), the bucket and chunk
+ * counts and the workspace sizes follow c and S; results do not depend on the setting.  Any other value is BGLS_ERR_ARG and leaves the
+ * setting as it was.  Needs no device.  Returns 0. */
+int bgls_set_msm_plan(int c, int S);
 /* verifyMultiSignature over ScalePoints(keys, multiplicity) -- the body of KoskVerifyMultiSignatureWithMultiplicity
  * (bgls/blsKosk.go:137-150; that function prepends 0x01 to msg like KoskVerifyMultiSignature, the host mirror does
  * the same).  multiplicity: n int64 factors, negative = negate-then-multiply (curves/curve.go:190-214); NULL = plain
@@ -729,6 +734,13 @@ int bgls_selftest_exception_barrier(int kind);
  * allocated) to caps[0 .. min(n, slots)) and returns the slot count.  Test-only: no binding mirrors them. */
 int bgls_selftest_fill_workspaces(int byte, uint64_t keys, uint64_t* bytes_filled);
 int bgls_selftest_workspace_caps(size_t* caps, int n);
+/* What the last weighted sum (bgls_weighted_sum_dev, the hashed-exponent entries, bgls_verify_multi_multiplicity) on the calling thread's
+ * context did: out[0] = path (0 per-point form because n was below bgls_set_msm_min's threshold or n * windows reached 2^32, 1 bucket
+ * method, 2 per-point form after the histogram showed a bucket above max(8 (n >> c), 64)), out[1] = window bits c, out[2] = threads per
+ * bucket S, out[3] = windows W, out[4] = largest bucket, out[5] = listed (point, window) pairs; the last two are 0 for path 0.  All zero
+ * before the first sum; an empty sum reports nothing.  NULL is BGLS_ERR_ARG; without a device BGLS_ERR_NO_DEVICE.  Test-only: no
+ * binding mirrors it. */
+int bgls_selftest_msm_last(uint32_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,9 @@ def test_weighted_sum_bucket_method_against_oracle(gpu_lib, cid, group):
         pts = bytes(pts)
         want = oracle_wsum(cid, group, pts, w)
         assert wsum(lib, cid, group, pts, w, 0) == want, n              # bucket method whatever n
+        rep = (ctypes.c_uint32 * 6)()
+        # the bucket kernels ran, except at 700 (c = 6): the two-bit top window's three buckets alone send uniform weights to the per-point form
+        assert lib.bgls_selftest_msm_last(rep) == 0 and rep[0] == (2 if n == 700 else 1), (n, tuple(rep))
         assert wsum(lib, cid, group, pts, w, SIZE_MAX) == want, n       # one double-and-add per point
     # everything cancels: infinity
     sc = [rnd.randrange(1, ORDER[cid]) for _ in range(20)]
@@ -132,9 +135,14 @@ def test_weighted_sum_skewed_weights_fall_back(gpu_lib):
     g = out(4 * FP[cid]); lib.bgls_generator(cid, group, g)
     want = coracle.scale_point(cid, group, bytes(g), sum(a * b for a, b in zip(w, sc)) % r)
     assert wsum(lib, cid, group, pts, w, 0) == want
+    rep = (ctypes.c_uint32 * 6)()
+    assert lib.bgls_selftest_msm_last(rep) == 0
+    assert tuple(rep) == (2, 9, 1, 15, max(w.count(d) for d in range(1, 6)), n - w.count(0))     # per-point form after the imbalance test
     w = [(1 << 100) + 12345] * n                                      # one weight for everybody
     want = coracle.scale_point(cid, group, bytes(g), sum(a * b for a, b in zip(w, sc)) % r)
     assert wsum(lib, cid, group, pts, w, 0) == want
+    assert lib.bgls_selftest_msm_last(rep) == 0
+    assert tuple(rep)[:5] == (2, 9, 1, 15, n)
 
 
 @pytest.mark.parametrize("cid", [0, 1], ids=["altbn128", "bls12"])
