@@ -182,6 +182,29 @@ BGLS_FN Jac<F> jac_mul(const Aff<F>& p, const u32* k, int nbits) {
   return r;
 }
 
+// Signed radix-16 digit i of a scalar in N little-endian words, in [-8, 8]: bits 4 i - 1 .. 4 i + 3 (bit -1 is zero) as -8 b4 + the
+// low four rounded up to even, halved.  A window that straddles a word takes its high bits from the word above.  PADDED: the top
+// word is zero padding above the scalar, so that read needs no test (the clamp only shows the compiler that it stays inside);
+// otherwise bits above the top word read as zero.
+template <bool PADDED, int N>
+BGLS_HD int w4_digit(const u32 (&w)[N], int i) {
+  const int pos = 4 * i - 1;                       // bits pos .. pos + 4
+  u32 b5;
+  if (pos < 0) {
+    b5 = (w[0] << 1) & 31u;
+  } else {
+    const int q = pos >> 5, sh = pos & 31;
+    u32 lo = w[q] >> sh;
+    if (PADDED) {
+      if (sh > 27) lo |= w[q + 1 < N ? q + 1 : N - 1] << (32 - sh);
+    } else {
+      if (sh > 27 && q < N - 1) lo |= w[q + 1] << (32 - sh);
+    }
+    b5 = lo & 31u;
+  }
+  return (int)(((b5 & 15u) + 1u) >> 1) - (int)(b5 >> 4) * 8;
+}
+
 // k * P for a per-lane scalar of up to 256 bits (Point.Mul at the seam, curves/curve.go:190-214: the reference hands the
 // scalar to the curve library): signed radix-16 digits (Booth recoding: d_i = -8 k_{4i+3} + 4 k_{4i+2} + 2 k_{4i+1} + k_{4i} +
 // k_{4i-1}, in [-8, 8]) against a table P .. 8P.  Every window is four doublings and ONE general addition whatever the digit,
@@ -216,18 +239,7 @@ BGLS_FN Jac<F> jac_mul_w4(const Aff<F>& p, const u32* k, int nbits) {
       r = jac_dbl<F>(r);
       r = jac_dbl<F>(r);
     }
-    const int pos = 4 * i - 1;                     // bits pos .. pos + 4
-    u32 b5;
-    if (pos < 0) {
-      b5 = (w[0] << 1) & 31u;
-    } else {
-      const int q = pos >> 5, sh = pos & 31;
-      u32 lo = w[q] >> sh;
-      if (sh > 27) lo |= w[q + 1 < 9 ? q + 1 : 8] << (32 - sh);
-      b5 = lo & 31u;
-    }
-    const int mag = (int)(((b5 & 15u) + 1u) >> 1), neg8 = (int)(b5 >> 4) * 8;
-    const int val = mag - neg8;
+    const int val = w4_digit<true>(w, i);
     const int a = val < 0 ? -val : val;
     if (a) {
       Jac<F> q = tab[a - 1];

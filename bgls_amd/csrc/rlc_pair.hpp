@@ -40,7 +40,7 @@ struct RlcPt<C, true> {
   static BGLS_HD J dbl(const J& p) { return jac1_dbl<C>(p); }
   static BGLS_HD J madd(const J& p, const Aff<F>& q) { return jac1_madd<C>(p, aff1_from_mont<C>(q)); }
   static BGLS_HD J add(const J& p, const J& q) { return jac1_add<C>(p, q); }
-  static BGLS_HD void negate(J& q) { q.Y = sx_as<SX_F, C>(sx_norm<C>(sx_neg<C>(q.Y))); }
+  static BGLS_HD void negate(J& q) { q.Y = el_negf<C>(q.Y); }
   static BGLS_HD Jac<F> to_mont(const J& p) { return jac1_to_mont<C>(p); }
 };
 
@@ -52,21 +52,6 @@ BGLS_HD void rlc_scalar(const uint8_t* r16, u32 (&k)[4]) {
     k[j] = ((u32)q[0] << 24) | ((u32)q[1] << 16) | ((u32)q[2] << 8) | (u32)q[3];
   }
   k[0] |= 1u;
-}
-
-// signed radix-16 digit i (0 .. 32) of a 128-bit scalar: bits 4 i - 1 .. 4 i + 3, in [-8, 8]
-BGLS_HD int rlc_digit(const u32 (&k)[4], int i) {
-  const int pos = 4 * i - 1;
-  u32 b5;
-  if (pos < 0) {
-    b5 = (k[0] << 1) & 31u;
-  } else {
-    const int q = pos >> 5, sh = pos & 31;
-    u32 lo = k[q] >> sh;
-    if (sh > 27 && q < 3) lo |= k[q + 1] << (32 - sh);
-    b5 = lo & 31u;
-  }
-  return (int)(((b5 & 15u) + 1u) >> 1) - (int)(b5 >> 4) * 8;
 }
 
 // out[t] = k * p[t] for t = 0, 1 (Jacobian, Montgomery form; Z = 0 at infinity)
@@ -91,7 +76,7 @@ BGLS_FN void rlc_mul2(const Aff<F1<C>> (&p)[2], const u32 (&k)[4], Jac<F1<C>> (&
   }
 #pragma unroll 1
   for (int i = 32; i >= 0; --i) {
-    const int val = rlc_digit(k, i);               // one decomposition for both points
+    const int val = w4_digit<false>(k, i);         // one decomposition for both points; bits above word 3 read as zero
     const int a = val < 0 ? -val : val;
 #pragma unroll 1
     for (int t = 0; t < 2; ++t) {

@@ -1,5 +1,7 @@
-// G2 key sums on the carry-free 28-bit-limb arithmetic of rx.hpp: Fp2 on ONE lane (signed limbs, compile-time bounds) and the
-// Jacobian mixed addition a key sum is made of (AggregatePoints, curves/curve.go:73-121: n - 1 additions of unit-weight keys).
+// Points on ONE lane in the carry-free 28-bit-limb form of rx.hpp (signed limbs, compile-time bounds), over either coordinate field:
+// G1 over Fp (Sx, named jac1_* in rx_jac1.hpp) and the twists over Fp2 (X2, named jacx_* here; their chain in rx_g2mul.hpp).  One
+// Jacobian formula set (dbl-2009-l, madd-2007-bl, add-2007-bl) and one windowed chain, written in field operations that both element
+// types spell the same way.  Born as the G2 key sum (AggregatePoints, curves/curve.go:73-121: n - 1 additions of unit-weight keys).
 //
 // Why: the 32-bit form of this loop (points_inl.hpp jac_madd_inl) runs at 0.24 of the multiplier's peak -- three VALU
 // instructions per multiplier instruction, 256 registers with 70 spilled.  Here an Fp2 product is four interleaved
@@ -17,19 +19,25 @@ struct X2 {
   Sx<C, LB> c0, c1;
 };
 
+// ---- products: Fp
 template <class C, int LA, int LB>
-BGLS_HD X2<C, LA + LB> x2_add(const X2<C, LA>& a, const X2<C, LB>& b) { return {sx_add<C>(a.c0, b.c0), sx_add<C>(a.c1, b.c1)}; }
-template <class C, int LA, int LB>
-BGLS_HD X2<C, LA + LB> x2_sub(const X2<C, LA>& a, const X2<C, LB>& b) { return {sx_sub<C>(a.c0, b.c0), sx_sub<C>(a.c1, b.c1)}; }
-template <int K, class C, int LA>
-BGLS_HD X2<C, K * LA> x2_mulc(const X2<C, LA>& a) { return {sx_mulc<K, C>(a.c0), sx_mulc<K, C>(a.c1)}; }
+BGLS_HD Sx<C, SX_T> s1_mul(const Sx<C, LA>& a, const Sx<C, LB>& b) {
+  const i32* const cols[1] = {b.v};
+  return sx_montr<C, 1, LA * LB>(cols, [&](int, int i) { return a.v[i]; });
+}
 template <class C, int LA>
-BGLS_HD X2<C, SX_F> x2_normf(const X2<C, LA>& a) { return {sx_normf<C>(a.c0), sx_normf<C>(a.c1)}; }
-template <class C, int LA>
-BGLS_HD X2<C, LA> x2_select(bool c, const X2<C, LA>& a, const X2<C, LA>& b) { return {sx_select<C>(c, a.c0, b.c0), sx_select<C>(c, a.c1, b.c1)}; }
-template <int LB, class C, int LA>
-BGLS_HD X2<C, LB> x2_as(const X2<C, LA>& a) { return {sx_as<LB, C>(a.c0), sx_as<LB, C>(a.c1)}; }
+BGLS_HD Sx<C, SX_T> s1_sqr(const Sx<C, LA>& a) {
+  const i32* const cols[1] = {a.v};
+  return sx_montr<C, 1, LA * LA>(cols, [&](int, int i) { return a.v[i]; });
+}
+// a b - c d, one reduction
+template <class C, int LA, int LB, int LC, int LD>
+BGLS_HD Sx<C, SX_T> s1_mulsub(const Sx<C, LA>& a, const Sx<C, LB>& b, const Sx<C, LC>& c, const Sx<C, LD>& d) {
+  const i32* const cols[2] = {b.v, d.v};
+  return sx_montr<C, 2, LA * LB + LC * LD>(cols, [&](int k, int i) { return k == 0 ? a.v[i] : -c.v[i]; });
+}
 
+// ---- products: Fp2
 // a * b: (a0 b0 - a1 b1) + (a0 b1 + a1 b0) i, two products and one reduction per component
 template <class C, int LA, int LB>
 BGLS_HD X2<C, SX_T> x2_mul(const X2<C, LA>& a, const X2<C, LB>& b) {
@@ -74,11 +82,64 @@ BGLS_HD X2<C, SX_T> x2_mulsub(const X2<C, LA>& a, const X2<C, LB>& b, const X2<C
   return r;
 }
 
+// widen the static bound (no code), as rx.hpp's sx_as
+template <int LB, class C, int LA>
+BGLS_HD X2<C, LB> x2_as(const X2<C, LA>& a) { return {sx_as<LB, C>(a.c0), sx_as<LB, C>(a.c1)}; }
+
+// ---- one spelling for both fields: what the point formulas below are written in.  Fp forwards to rx.hpp's sx_* and the s1_* above,
+// Fp2 works component-wise around the x2_* above; no arithmetic of its own.
+template <class C, int LA, int LB>
+BGLS_HD Sx<C, SX_T> el_mul(const Sx<C, LA>& a, const Sx<C, LB>& b) { return s1_mul<C>(a, b); }
+template <class C, int LA, int LB>
+BGLS_HD X2<C, SX_T> el_mul(const X2<C, LA>& a, const X2<C, LB>& b) { return x2_mul<C>(a, b); }
 template <class C, int LA>
-BGLS_HD bool x2_is_zero(const X2<C, LA>& a) { return sx_is_zero_mod_p<C>(a.c0) && sx_is_zero_mod_p<C>(a.c1); }
+BGLS_HD Sx<C, SX_T> el_sqr(const Sx<C, LA>& a) { return s1_sqr<C>(a); }
+template <class C, int LA>
+BGLS_HD X2<C, SX_T> el_sqr(const X2<C, LA>& a) { return x2_sqr<C>(a); }
+template <class C, int LA, int LB, int LC, int LD>
+BGLS_HD Sx<C, SX_T> el_mulsub(const Sx<C, LA>& a, const Sx<C, LB>& b, const Sx<C, LC>& c, const Sx<C, LD>& d) { return s1_mulsub<C>(a, b, c, d); }
+template <class C, int LA, int LB, int LC, int LD>
+BGLS_HD X2<C, SX_T> el_mulsub(const X2<C, LA>& a, const X2<C, LB>& b, const X2<C, LC>& c, const X2<C, LD>& d) { return x2_mulsub<C>(a, b, c, d); }
+template <class C, int LA, int LB>
+BGLS_HD Sx<C, LA + LB> el_add(const Sx<C, LA>& a, const Sx<C, LB>& b) { return sx_add<C>(a, b); }
+template <class C, int LA, int LB>
+BGLS_HD X2<C, LA + LB> el_add(const X2<C, LA>& a, const X2<C, LB>& b) { return {sx_add<C>(a.c0, b.c0), sx_add<C>(a.c1, b.c1)}; }
+template <class C, int LA, int LB>
+BGLS_HD Sx<C, LA + LB> el_sub(const Sx<C, LA>& a, const Sx<C, LB>& b) { return sx_sub<C>(a, b); }
+template <class C, int LA, int LB>
+BGLS_HD X2<C, LA + LB> el_sub(const X2<C, LA>& a, const X2<C, LB>& b) { return {sx_sub<C>(a.c0, b.c0), sx_sub<C>(a.c1, b.c1)}; }
+template <int K, class C, int LA>
+BGLS_HD Sx<C, K * LA> el_mulc(const Sx<C, LA>& a) { return sx_mulc<K, C>(a); }
+template <int K, class C, int LA>
+BGLS_HD X2<C, K * LA> el_mulc(const X2<C, LA>& a) { return {sx_mulc<K, C>(a.c0), sx_mulc<K, C>(a.c1)}; }
+template <class C, int LA>
+BGLS_HD Sx<C, SX_F> el_normf(const Sx<C, LA>& a) { return sx_normf<C>(a); }
+template <class C, int LA>
+BGLS_HD X2<C, SX_F> el_normf(const X2<C, LA>& a) { return {sx_normf<C>(a.c0), sx_normf<C>(a.c1)}; }
+// widen the static bound (no code)
+template <int LB, class C, int LA>
+BGLS_HD Sx<C, LB> el_as(const Sx<C, LA>& a) { return sx_as<LB, C>(a); }
+template <int LB, class C, int LA>
+BGLS_HD X2<C, LB> el_as(const X2<C, LA>& a) { return x2_as<LB, C>(a); }
+template <class C, int LA>
+BGLS_HD bool el_is_zero(const Sx<C, LA>& a) { return sx_is_zero_mod_p<C>(a); }
+template <class C, int LA>
+BGLS_HD bool el_is_zero(const X2<C, LA>& a) { return sx_is_zero_mod_p<C>(a.c0) && sx_is_zero_mod_p<C>(a.c1); }
 // for components in (-11 p, 13 p): differences against a doubling's X and Y (rx.hpp sx_is_zero_mod_p_wide)
 template <class C, int LA>
-BGLS_HD bool x2_is_zero_wide(const X2<C, LA>& a) { return sx_is_zero_mod_p_wide<C>(a.c0) && sx_is_zero_mod_p_wide<C>(a.c1); }
+BGLS_HD bool el_is_zero_wide(const Sx<C, LA>& a) { return sx_is_zero_mod_p_wide<C>(a); }
+template <class C, int LA>
+BGLS_HD bool el_is_zero_wide(const X2<C, LA>& a) { return sx_is_zero_mod_p_wide<C>(a.c0) && sx_is_zero_mod_p_wide<C>(a.c1); }
+// -a with the limbs tight again (the sign sits in the top limb)
+template <class C, int LA>
+BGLS_HD Sx<C, SX_F> el_negf(const Sx<C, LA>& a) { return sx_as<SX_F, C>(sx_norm<C>(sx_neg<C>(a))); }
+template <class C, int LA>
+BGLS_HD X2<C, SX_F> el_negf(const X2<C, LA>& a) { return {el_negf<C>(a.c0), el_negf<C>(a.c1)}; }
+// a base-field value as an element
+template <class C>
+BGLS_HD void el_set(Sx<C, SX_F>& r, const Sx<C, SX_T>& a) { r = sx_as<SX_F, C>(a); }
+template <class C>
+BGLS_HD void el_set(X2<C, SX_F>& r, const Sx<C, SX_T>& a) { r = {sx_as<SX_F, C>(a), sx_as<SX_F, C>(ux_to_sx<C>(ux_zero<C>()))}; }
 
 // x R (the library's Montgomery form) -> R' form
 template <class C>
@@ -101,25 +162,183 @@ BGLS_HD Fp<C> sx_to_mont(const Sx<C, LA>& a) {
   return from_ux<C>(u);
 }
 
-// running sum of a key-sum thread: Jacobian (X, Y, Z) over Fp2, limbs almost tight, plus the infinity flag
-template <class C>
-struct JacX {
-  X2<C, SX_F> X, Y, Z;
+// ===================================================================================================== points over either field
+// Jacobian (X, Y, Z), limbs almost tight, plus the infinity flag (the running sum of a key-sum thread, the entries of a chain's table)
+template <template <class, int> class E, class C>
+struct JacE {
+  E<C, SX_F> X, Y, Z;
   bool inf;
 };
-template <class C>
-struct AffX {
-  X2<C, SX_T> x, y;
+template <template <class, int> class E, class C>
+struct AffE {
+  E<C, SX_T> x, y;
   bool inf;
 };
-template <class C>
-BGLS_HD JacX<C> jacx_inf() {
-  JacX<C> r;
-  const Sx<C, SX_F> z = sx_as<SX_F, C>(ux_to_sx<C>(ux_zero<C>()));
-  r.X = {z, z}; r.Y = {z, z}; r.Z = {z, z};
+template <class C> using JacX = JacE<X2, C>;       // the twist, over Fp2 (G1 over Fp: Jac1 / Aff1, rx_jac1.hpp)
+template <class C> using AffX = AffE<X2, C>;
+
+// A field's own from_aff / dbl / madd / add: the jacx_* at the end of this header and the jac1_* of rx_jac1.hpp, each behind the attribute measured for
+// it.  The formulas reach their rare branches, and the chain every step, through here, so that they land on exactly those functions.
+template <template <class, int> class E, class C>
+struct JacLaw;
+
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_inf() {
+  JacE<E, C> r;
+  el_set<C>(r.X, ux_to_sx<C>(ux_zero<C>()));
+  r.Y = r.X; r.Z = r.X;
   r.inf = true;
   return r;
 }
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_from_aff(const AffE<E, C>& q) {
+  JacE<E, C> r;
+  r.X = el_as<SX_F, C>(q.x);
+  r.Y = el_as<SX_F, C>(q.y);
+  el_set<C>(r.Z, sx_const<C>(C::RX_ONE));
+  r.inf = q.inf;
+  return r;
+}
+
+// 2 p (dbl-2009-l, a = 0): 2 products + 5 squarings
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_dbl(const JacE<E, C>& p) {
+  typedef E<C, SX_T> T;
+  typedef E<C, SX_F> F;
+  if (p.inf) return p;
+  const T A = el_sqr<C>(p.X), B = el_sqr<C>(p.Y), Cc = el_sqr<C>(B);
+  const F D = el_normf<C>(el_mulc<2, C>(el_sub<C>(el_sub<C>(el_sqr<C>(el_normf<C>(el_add<C>(p.X, B))), A), Cc)));
+  const F Ee = el_normf<C>(el_mulc<3, C>(A));
+  const T Ff = el_sqr<C>(Ee);
+  JacE<E, C> r;
+  r.X = el_normf<C>(el_sub<C>(Ff, el_mulc<2, C>(D)));
+  r.Y = el_normf<C>(el_sub<C>(el_mul<C>(Ee, el_normf<C>(el_sub<C>(D, r.X))), el_mulc<2, C>(el_normf<C>(el_mulc<4, C>(Cc)))));
+  r.Z = el_normf<C>(el_mulc<2, C>(el_mul<C>(p.Y, p.Z)));
+  r.inf = false;
+  return r;
+}
+
+// p + q, q affine (madd-2007-bl): 7 products + 4 squarings (over Fp2: 56 units of NL^2 multiplier instructions)
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_madd(const JacE<E, C>& p, const AffE<E, C>& q) {
+  typedef E<C, SX_T> T;
+  typedef E<C, SX_F> F;
+  if (q.inf) return p;
+  if (p.inf) return jace_from_aff<E, C>(q);
+  const T Z1Z1 = el_sqr<C>(p.Z);
+  const T U2 = el_mul<C>(q.x, Z1Z1);
+  const T S2 = el_mul<C>(el_mul<C>(q.y, p.Z), Z1Z1);
+  const auto Hd = el_sub<C>(U2, p.X);
+  const auto Rd = el_sub<C>(S2, p.Y);
+  if (el_is_zero_wide<C>(Hd)) {                                // same x: P = Q (double) or P = -Q (infinity); p may be a doubling's
+    if (el_is_zero_wide<C>(Rd)) return JacLaw<E, C>::dbl(p);   // output: X up to 9 p, Y down to -8 p
+    return jace_inf<E, C>();
+  }
+  const F H = el_normf<C>(Hd);
+  const F rr = el_normf<C>(el_mulc<2, C>(Rd));
+  const T HH = el_sqr<C>(H);
+  const F I = el_normf<C>(el_mulc<4, C>(HH));
+  const T J = el_mul<C>(H, I);
+  const T V = el_mul<C>(p.X, I);
+  JacE<E, C> r;
+  r.X = el_normf<C>(el_sub<C>(el_sub<C>(el_sqr<C>(rr), J), el_mulc<2, C>(V)));
+  r.Y = el_as<SX_F, C>(el_mulsub<C>(rr, el_normf<C>(el_sub<C>(V, r.X)), el_mulc<2, C>(p.Y), J));
+  r.Z = el_normf<C>(el_sub<C>(el_sub<C>(el_sqr<C>(el_normf<C>(el_add<C>(p.Z, H))), Z1Z1), HH));
+  r.inf = false;
+  return r;
+}
+
+// p + q, both Jacobian (add-2007-bl): 11 products + 5 squarings
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_add(const JacE<E, C>& p, const JacE<E, C>& q) {
+  typedef E<C, SX_T> T;
+  typedef E<C, SX_F> F;
+  if (q.inf) return p;
+  if (p.inf) return q;
+  const T Z1Z1 = el_sqr<C>(p.Z), Z2Z2 = el_sqr<C>(q.Z);
+  const T U1 = el_mul<C>(p.X, Z2Z2), U2 = el_mul<C>(q.X, Z1Z1);
+  const T S1 = el_mul<C>(el_mul<C>(p.Y, q.Z), Z2Z2), S2 = el_mul<C>(el_mul<C>(q.Y, p.Z), Z1Z1);
+  const auto Hd = el_sub<C>(U2, U1);
+  const auto Rd = el_sub<C>(S2, S1);
+  if (el_is_zero<C>(Hd)) {                                     // same x: P = Q (double) or P = -Q (infinity)
+    if (el_is_zero<C>(Rd)) return JacLaw<E, C>::dbl(p);
+    return jace_inf<E, C>();
+  }
+  const F H = el_normf<C>(Hd);
+  const F rr = el_normf<C>(el_mulc<2, C>(Rd));
+  const F I = el_normf<C>(el_mulc<4, C>(el_sqr<C>(H)));
+  const T J = el_mul<C>(H, I);
+  const T V = el_mul<C>(U1, I);
+  JacE<E, C> r;
+  r.X = el_normf<C>(el_sub<C>(el_sub<C>(el_sqr<C>(rr), J), el_mulc<2, C>(V)));
+  r.Y = el_as<SX_F, C>(el_mulsub<C>(rr, el_normf<C>(el_sub<C>(V, r.X)), el_mulc<2, C>(S1), J));
+  r.Z = el_as<SX_F, C>(el_mul<C>(el_normf<C>(el_sub<C>(el_sub<C>(el_sqr<C>(el_normf<C>(el_add<C>(p.Z, q.Z))), Z1Z1), Z2Z2)), H));
+  r.inf = false;
+  return r;
+}
+
+// k * P for a per-lane scalar of up to 256 bits (k: eight little-endian words, nbits: the position of the top set bit + 1):
+// curve.hpp's jac_mul_w4 (signed radix-16 digits against P .. 8P, four doublings and ONE general addition per window whatever
+// the digit) on this arithmetic.  Same point as curve.hpp's jac_mul / jac_mul_w4.
+template <template <class, int> class E, class C>
+BGLS_HD JacE<E, C> jace_mul_w4(const AffE<E, C>& p, const u32* k, int nbits) {
+  typedef JacLaw<E, C> L;
+  if (p.inf || nbits <= 0) return jace_inf<E, C>();
+  u32 w[9];
+  const int nl = (nbits + 31) >> 5;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) w[j] = j < nl && j < 8 ? k[j] : 0u;
+  if (nbits & 31) w[nl - 1] &= (1u << (nbits & 31)) - 1u;
+  JacE<E, C> tab[8];                               // tab[a - 1] = a P
+  tab[0] = L::from_aff(p);
+  tab[1] = L::dbl(tab[0]);
+  tab[2] = L::madd(tab[1], p);
+  tab[3] = L::dbl(tab[1]);
+  tab[4] = L::madd(tab[3], p);
+  tab[5] = L::dbl(tab[2]);
+  tab[6] = L::madd(tab[5], p);
+  tab[7] = L::dbl(tab[3]);
+  const int nw = (nbits + 4) >> 2;                 // one bit above the scalar: the top window's sign bit is clear
+  JacE<E, C> r = jace_inf<E, C>();
+#pragma unroll 1
+  for (int i = nw - 1; i >= 0; --i) {
+    if (i != nw - 1) {
+#pragma unroll 1
+      for (int d = 0; d < 4; ++d) r = L::dbl(r);
+    }
+    const int val = w4_digit<true>(w, i);
+    const int a = val < 0 ? -val : val;
+    if (a) {
+      JacE<E, C> q = tab[a - 1];
+      if (val < 0) q.Y = el_negf<C>(q.Y);
+      r = L::add(r, q);
+    }
+  }
+  return r;
+}
+
+// ===================================================================================================== the twists, over Fp2
+template <class C>
+BGLS_HD JacX<C> jacx_inf() { return jace_inf<X2, C>(); }
+template <class C>
+BGLS_HD JacX<C> jacx_from_aff(const AffX<C>& q) {
+  if (q.inf) return jacx_inf<C>();
+  return jace_from_aff<X2, C>(q);
+}
+// the rare branch of the mixed addition (a key met twice in one thread's slice), every step of the chain
+template <class C>
+BGLS_FN JacX<C> jacx_dbl(const JacX<C>& p) { return jace_dbl<X2, C>(p); }
+template <class C>
+BGLS_HD JacX<C> jacx_madd(const JacX<C>& p, const AffX<C>& q) { return jace_madd<X2, C>(p, q); }
+template <class C>
+BGLS_FN JacX<C> jacx_add(const JacX<C>& p, const JacX<C>& q) { return jace_add<X2, C>(p, q); }
+template <class C>
+struct JacLaw<X2, C> {
+  static BGLS_HD JacX<C> from_aff(const AffX<C>& q) { return jacx_from_aff<C>(q); }
+  static BGLS_HD JacX<C> dbl(const JacX<C>& p) { return jacx_dbl<C>(p); }
+  static BGLS_HD JacX<C> madd(const JacX<C>& p, const AffX<C>& q) { return jacx_madd<C>(p, q); }
+  static BGLS_HD JacX<C> add(const JacX<C>& p, const JacX<C>& q) { return jacx_add<C>(p, q); }
+};
 
 // y^2 = x^3 + b' on the twist
 template <class C>
@@ -127,61 +346,8 @@ BGLS_HD bool affx_on_curve(const AffX<C>& q) {
   if (q.inf) return true;
   const X2<C, SX_T> b2 = {sx_const<C>(C::RX_B2_RE), sx_const<C>(C::RX_B2_IM)};
   const X2<C, SX_T> x3 = x2_mul<C>(x2_sqr<C>(q.x), q.x);
-  return x2_is_zero<C>(x2_sub<C>(x2_sqr<C>(q.y), x2_add<C>(x3, b2)));
+  return el_is_zero<C>(el_sub<C>(x2_sqr<C>(q.y), el_add<C>(x3, b2)));
 }
-
-// 2 p (dbl-2009-l); the rare branch of the mixed addition (a key met twice in one thread's slice)
-template <class C>
-BGLS_FN JacX<C> jacx_dbl(const JacX<C>& p) {
-  if (p.inf) return p;
-  const X2<C, SX_T> A = x2_sqr<C>(p.X), B = x2_sqr<C>(p.Y), Cc = x2_sqr<C>(B);
-  const X2<C, SX_F> D = x2_normf<C>(x2_mulc<2, C>(x2_sub<C>(x2_sub<C>(x2_sqr<C>(x2_normf<C>(x2_add<C>(p.X, B))), A), Cc)));
-  const X2<C, SX_F> E = x2_normf<C>(x2_mulc<3, C>(A));
-  const X2<C, SX_T> F = x2_sqr<C>(E);
-  JacX<C> r;
-  r.X = x2_normf<C>(x2_sub<C>(F, x2_mulc<2, C>(D)));
-  r.Y = x2_normf<C>(x2_sub<C>(x2_mul<C>(E, x2_normf<C>(x2_sub<C>(D, r.X))), x2_mulc<2, C>(x2_normf<C>(x2_mulc<4, C>(Cc)))));
-  r.Z = x2_normf<C>(x2_mulc<2, C>(x2_mul<C>(p.Y, p.Z)));
-  r.inf = false;
-  return r;
-}
-
-// p + q, q affine (madd-2007-bl), 56 units of NL^2 multiplier instructions
-template <class C>
-BGLS_HD JacX<C> jacx_madd(const JacX<C>& p, const AffX<C>& q) {
-  if (q.inf) return p;
-  if (p.inf) {
-    JacX<C> r;
-    r.X = x2_as<SX_F, C>(q.x);
-    r.Y = x2_as<SX_F, C>(q.y);
-    const Sx<C, SX_F> z = sx_as<SX_F, C>(ux_to_sx<C>(ux_zero<C>()));
-    r.Z = {sx_as<SX_F, C>(sx_const<C>(C::RX_ONE)), z};
-    r.inf = false;
-    return r;
-  }
-  const X2<C, SX_T> Z1Z1 = x2_sqr<C>(p.Z);
-  const X2<C, SX_T> U2 = x2_mul<C>(q.x, Z1Z1);
-  const X2<C, SX_T> S2 = x2_mul<C>(x2_mul<C>(q.y, p.Z), Z1Z1);
-  const auto Hd = x2_sub<C>(U2, p.X);
-  const auto Rd = x2_sub<C>(S2, p.Y);
-  if (x2_is_zero_wide<C>(Hd)) {                                // same x: P = Q (double) or P = -Q (infinity); p may be a doubling's
-    if (x2_is_zero_wide<C>(Rd)) return jacx_dbl<C>(p);         // output: X up to 9 p, Y down to -8 p
-    return jacx_inf<C>();
-  }
-  const X2<C, SX_F> H = x2_normf<C>(Hd);
-  const X2<C, SX_F> rr = x2_normf<C>(x2_mulc<2, C>(Rd));
-  const X2<C, SX_T> HH = x2_sqr<C>(H);
-  const X2<C, SX_F> I = x2_normf<C>(x2_mulc<4, C>(HH));
-  const X2<C, SX_T> J = x2_mul<C>(H, I);
-  const X2<C, SX_T> V = x2_mul<C>(p.X, I);
-  JacX<C> r;
-  r.X = x2_normf<C>(x2_sub<C>(x2_sub<C>(x2_sqr<C>(rr), J), x2_mulc<2, C>(V)));
-  r.Y = x2_as<SX_F, C>(x2_mulsub<C>(rr, x2_normf<C>(x2_sub<C>(V, r.X)), x2_mulc<2, C>(p.Y), J));
-  r.Z = x2_normf<C>(x2_sub<C>(x2_sub<C>(x2_sqr<C>(x2_normf<C>(x2_add<C>(p.Z, H))), Z1Z1), HH));
-  r.inf = false;
-  return r;
-}
-
 // wire bytes (x_im || x_re || y_im || y_re, big-endian; all zero = infinity) -> R' form; false when a coordinate is not canonical
 template <class C>
 BGLS_HD bool affx_from_bytes(AffX<C>& out, const uint8_t* b) {

@@ -36,6 +36,7 @@ def cases(cid):
     for i, d in ((0, 1), (0, 7), (5, 7), (17, 3), (31, 5), (31, 7)):           # a single non-zero window digit d at window i
         out.append(("single digit %d at window %d" % (d, i), H, S, d << (4 * i), 0))
     out.append(("r = 2^127 (digit -8 at window 31, the carry into window 32)", H, S, 1 << 127, 0))
+    out.append(("r = 2^127 + 1 (the top bit of the top word and the bit under window 0)", H, S, (1 << 127) | 1, 0))
     out.append(("sigma = -H", H, cv.neg(H), rnd.getrandbits(128) | 1, 0))
     out.append(("sigma = H", H, H, rnd.getrandbits(128) | 1, 0))
     out.append(("even r, lowest bit set by rlc_scalar", H, S, rnd.getrandbits(128) & ~1, 1))
