@@ -82,6 +82,9 @@ SIGNATURES = {
     "bgls_check_points": (ci, [ci, ci, u8p, sz, u8p]),
     "bgls_select_device": (ci, [ci]),
     "bgls_keys_upload": (ci, [ci, u8p, sz, ctypes.POINTER(ctypes.c_int), ci, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint64)]),
+    "bgls_keys_upload_compressed": (ci, [ci, u8p, sz, ctypes.POINTER(ctypes.c_int), ci, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(sz)]),
+    "bgls_keys_read": (ci, [ctypes.c_uint64, sz, sz, u8p]),
+    "bgls_decompress_points_dev": (ci, [ci, ci, vp, sz, vp, vp, vp]),
     "bgls_keys_free": (ci, [ctypes.c_uint64]),
     "bgls_keys_info": (ci, [ctypes.c_uint64, ctypes.POINTER(ci), ctypes.POINTER(sz), ctypes.POINTER(ci)]),
     "bgls_verify_aggregate_h": (ci, [ctypes.c_uint64, u8p, u8p, u64p, sz, ci]),

@@ -51,6 +51,37 @@ class KeySet:
             raise ValueError("bgls_keys_upload: %d %s" % (rc, _lib.last_error()))
         self.curve, self.n, self.handle = curve, n, h.value
 
+    @classmethod
+    def from_compressed(cls, curve, keys, devices=None, prepare=False):
+        """A key set from compressed keys (Point.Marshal: 64 / 96 bytes each; bytes or a list of encodings), decoded and validated on the
+        device(s) in one pass as UnmarshalG2 does (bgls_keys_upload_compressed).  ValueError names the first refused key."""
+        raw = bytes(keys) if isinstance(keys, (bytes, bytearray, memoryview)) else b"".join(bytes(k) for k in keys)
+        cb = 2 * curve.fp_bytes
+        if len(raw) % cb:
+            raise ValueError("compressed keys: %d bytes is not a multiple of %d" % (len(raw), cb))
+        n = len(raw) // cb
+        h, bad = ctypes.c_uint64(), ctypes.c_size_t(n)
+        devs = list(devices) if devices else None
+        rc = _lib.load().bgls_keys_upload_compressed(curve.id, _lib.buf(raw), n, (ctypes.c_int * len(devs))(*devs) if devs else None, len(devs) if devs else 1,
+                                                     2 if prepare else 0, ctypes.byref(h), ctypes.byref(bad))
+        if rc == -2 and bad.value < n:
+            raise ValueError("bgls_keys_upload_compressed: key %d was refused: %s" % (bad.value, _lib.last_error()))
+        if rc != 0:
+            raise ValueError("bgls_keys_upload_compressed: %d %s" % (rc, _lib.last_error()))
+        self = cls.__new__(cls)
+        self.curve, self.n, self.handle = curve, n, h.value
+        return self
+
+    def keys(self):
+        """the set's keys as Points, read back from the device(s) (bgls_keys_read)"""
+        gb = 4 * self.curve.fp_bytes
+        out = (ctypes.c_uint8 * max(1, self.n * gb))()
+        rc = _lib.load().bgls_keys_read(self.handle, 0, self.n, out)
+        if rc != 0:
+            raise ValueError("bgls_keys_read: %d %s" % (rc, _lib.last_error()))
+        raw = bytes(out)
+        return [Point(self.curve, G2, raw[i * gb:(i + 1) * gb]) for i in range(self.n)]
+
     def __len__(self):
         return self.n
 

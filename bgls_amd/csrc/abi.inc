@@ -442,6 +442,25 @@ int bgls_keys_upload(int curve, const uint8_t* keys, size_t n, const int* device
   DISPATCH(curve, keys_upload_t<CV>(keys, n, devices, n_devices, flags, handle_out));
 } BGLS_ABI_GUARD
 
+int bgls_keys_upload_compressed(int curve, const uint8_t* keys_c, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* handle_out,
+                                size_t* first_bad) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (!handle_out || (n && !keys_c)) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (n_devices < 1 || n_devices > NCTX) return fail(BGLS_ERR_ARG, "n_devices out of range (1..16)");
+  int dflt = cur_device();
+  if (!devices && n_devices == 1) devices = &dflt;
+  DISPATCH(curve, keys_upload_t<CV>(keys_c, n, devices, n_devices, flags | BGLS_KEYS_CHECK, handle_out, true, first_bad));
+} BGLS_ABI_GUARD
+
+int bgls_keys_read(bgls_keys_t handle, size_t first, size_t count, uint8_t* out) try {
+  auto ks = keyset(handle);
+  if (!ks) return fail(BGLS_ERR_ARG, "unknown key-set handle");
+  if (first > ks->n || count > ks->n - first) return fail(BGLS_ERR_ARG, "key range beyond the set");
+  if (count && !out) return fail(BGLS_ERR_ARG, "NULL argument");
+  if (count == 0) return 0;
+  DISPATCH(ks->curve, keys_read_t<CV>(*ks, first, count, out));
+} BGLS_ABI_GUARD
+
 int bgls_keys_free(bgls_keys_t handle) try {
   std::shared_ptr<KeySet> ks;
   {
@@ -1116,6 +1135,13 @@ int bgls_decompress_points(int curve, int group, const uint8_t* in, size_t n, ui
   if (n >= MAX_BATCH) return too_large();
   if (!group_ok(group) || (n && (!in || !out || !ok))) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
   return wire_points(curve, group, false, in, n, out, ok);
+} BGLS_ABI_GUARD
+
+int bgls_decompress_points_dev(int curve, int group, const void* d_in, size_t n, void* d_out, void* d_ok, void* stream) try {
+  if (n >= MAX_BATCH) return too_large();
+  if (n == 0) return 0;
+  if (!group_ok(group) || !d_in || !d_out || !d_ok) return fail(BGLS_ERR_ARG, "bad group or NULL argument");
+  DISPATCH(curve, decompress_points_dev_t<CV>(group, d_in, n, d_out, d_ok, stream));
 } BGLS_ABI_GUARD
 
 /* ---- batch key generation / signing (bgls/bgls.go:40-56) ---- */

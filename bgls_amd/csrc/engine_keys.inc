@@ -98,8 +98,12 @@ struct PrepShape { size_t ng = 0, chunk = 0; };
 std::mutex g_prep_shape_mu;
 PrepShape g_prep_shape;
 
+// compressed: `keys` holds Point.Marshal encodings (E::G2B / 2 bytes each); each shard decodes its range with the one-pass kernel of
+// k_wirex.hip, which validates every key and writes d_wire and d_mont itself (bgls_keys_upload_compressed).  *first_bad: the smallest
+// refused index -- the shards are walked in index order and the walk stops at the first that refuses a key.
 template <class C>
-int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* out) {
+int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* out, bool compressed = false,
+                  size_t* first_bad = nullptr) {
   typedef Engine<C> E;
   if (n >= MAX_BATCH) return fail(BGLS_ERR_ARG, "key set too large (n must be below 2^30)");
   auto ks = std::make_shared<KeySet>();
@@ -142,15 +146,30 @@ int keys_upload_t(const uint8_t* keys, size_t n, const int* devices, int n_devic
       void* d_flags;
       if ((r = c.get(WS_FLAGS, 16, &d_flags))) return r;
       HIPCHK(hipMemsetAsync(d_flags, 0, 4, c.stream));
-      if (cnt) {
+      uint32_t* d_bad = (uint32_t*)d_flags + 1;             // compressed: the smallest refused index of this shard (atomicMin)
+      if (cnt && compressed) {
+        const size_t CB = E::G2B / 2;
+        void* d_comp;
+        if ((r = c.get(WS_IN_B, cnt * CB, &d_comp))) return r;
+        HIPCHK(hipMemsetAsync(d_bad, 0xFF, 4, c.stream));
+        HIPCHK(hipMemcpyAsync(d_comp, keys + sh.lo * CB, cnt * CB, hipMemcpyHostToDevice, c.stream));
+        kl::wirex_decode<C>(c.stream, BGLS_G2, (const uint8_t*)d_comp, cnt, (uint8_t*)sh.d_wire, nullptr, sh.d_mont, d_bad);
+        kl::g2_sumready<C>(c.stream, sh.d_mont, cnt, sh.d_sumr);
+        HIPCHK(hipGetLastError());
+      } else if (cnt) {
         HIPCHK(hipMemcpyAsync(sh.d_wire, keys + sh.lo * E::G2B, cnt * E::G2B, hipMemcpyHostToDevice, c.stream));
         kl::g2_parse<C>(c.stream, (const uint8_t*)sh.d_wire, cnt, (flags & BGLS_KEYS_CHECK) ? 1 : 0, sh.d_mont, (uint32_t*)d_flags);
         kl::g2_sumready<C>(c.stream, sh.d_mont, cnt, sh.d_sumr);
         HIPCHK(hipGetLastError());
       }
-      uint32_t f = 0;
+      uint32_t f = 0, bad = 0xFFFFFFFFu;
       HIPCHK(hipMemcpyAsync(&f, d_flags, 4, hipMemcpyDeviceToHost, c.stream));
+      if (cnt && compressed) HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c.stream));
       HIPCHK(hipStreamSynchronize(c.stream));
+      if (bad != 0xFFFFFFFFu) {
+        if (first_bad) *first_bad = sh.lo + bad;
+        return fail(BGLS_ERR_ENCODING, "key set: a compressed key was refused (encoding, not on the twist, or outside the order-r subgroup)");
+      }
       if (f & FLAG_ENC) return fail(BGLS_ERR_ENCODING, "key set: non-canonical coordinate or key not on the twist");
       if (f & FLAG_SUBGROUP) return fail(BGLS_ERR_ENCODING, "key set: key outside the order-r subgroup");
       if (flags & BGLS_KEYS_PREPARE) {
@@ -705,6 +724,37 @@ int verify_aggregate_grouped_keys_dev_t(KeySet& ks, const void* d_sig, const voi
   const MsgView mv = {(const uint8_t*)d_msgs, nullptr, msg_len, msg_stride};
   return verify_aggregate_grouped_keys_run<C>(k.c, k.st, ks, (const uint8_t*)d_sig, (const uint32_t*)d_bitmap, bitmap_len / 4, mv, n_msgs * msg_len, n_msgs,
                                               n_groups, gt_out);
+}
+
+// bgls_keys_read: the wire bytes of keys [first, first + count), each shard's part from its own d_wire
+template <class C>
+int keys_read_t(KeySet& ks, size_t first, size_t count, uint8_t* out) {
+  typedef Engine<C> E;
+  std::lock_guard<std::mutex> lk_set(ks.mu);
+  SelectionGuard keep_selection;
+  for (KeyShard& sh : ks.shards) {
+    const size_t a = first > sh.lo ? first : sh.lo, b = first + count < sh.hi ? first + count : sh.hi;
+    if (a >= b) continue;
+    g_dev = sh.device;
+    g_sel = 0;
+    Ctx& c = ctx();
+    std::lock_guard<std::mutex> lk(c.mu);
+    int r;
+    if ((r = c.enter())) return r;
+    HIPCHK(hipMemcpyAsync(out + (a - first) * E::G2B, (const uint8_t*)sh.d_wire + (a - sh.lo) * E::G2B, (b - a) * E::G2B, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+  }
+  return 0;
+}
+
+// bgls_decompress_points_dev: the one-pass kernel of k_wirex.hip over resident input; nothing is read back, nothing is awaited
+template <class C>
+int decompress_points_dev_t(int group, const void* d_in, size_t n, void* d_out, void* d_ok, void* stream) {
+  Call k(stream);
+  if (k.rc) return k.rc;
+  kl::wirex_decode<C>(k.st, group, (const uint8_t*)d_in, n, (uint8_t*)d_out, (uint8_t*)d_ok, nullptr, nullptr);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 bool group_ok(int g) { return g == BGLS_G1 || g == BGLS_G2; }

@@ -79,6 +79,10 @@ void decompress_bn(hipStream_t st, int group, const uint8_t* in, size_t n, uint8
 // ---- k_wire.hip   (BLS12-381 compressed forms, ebfull/pairing layout)
 void compress_bls(hipStream_t st, int group, const uint8_t* in, size_t n, uint8_t* out, uint32_t* flags);
 void decompress_bls(hipStream_t st, int group, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok);
+// ---- k_wirex.hip   (both curves' compressed forms on the carry-free limbs, wire_x.hpp: decompress + membership + key-set record in one pass)
+// out: n uncompressed points (zeros where refused), ok: n bytes or nullptr, mont: n records of g2_parse or nullptr (G2 only),
+// first_bad: one word the caller set to 0xFFFFFFFF, lowered to the smallest refused index (atomicMin), or nullptr
+template <class C> void wirex_decode(hipStream_t st, int group, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok, void* mont, uint32_t* first_bad);
 void mad_probe(hipStream_t st, unsigned blocks, unsigned threads, uint32_t seed, int iters, uint64_t* sink);
 template <class C> size_t jac_bytes(int group) { return (size_t)3 * (group == 1 ? 1 : 2) * C::L * 4; }
 

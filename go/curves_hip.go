@@ -352,6 +352,63 @@ func HipUploadKeys(curve CurveSystem, keys []Point, devices []int, check bool) *
 	return ks
 }
 
+// HipUploadKeysCompressed makes a key set from compressed keys (Point.Marshal encodings, one per entry): every device decodes and
+// validates its range in one pass, as UnmarshalG2 does (bgls_keys_upload_compressed).  On a refused key the set is nil and the int is
+// the smallest refused index; -1 for every other failure.
+func HipUploadKeysCompressed(curve CurveSystem, keys [][]byte, devices []int, prepare bool) (*HipKeySet, int) {
+	c, ok := curve.(*hipCurve)
+	if !ok {
+		return nil, -1
+	}
+	cb := c.size(C.BGLS_G2) / 2
+	kb := make([]byte, 0, len(keys)*cb+1)
+	for _, k := range keys {
+		if len(k) != cb {
+			return nil, -1
+		}
+		kb = append(kb, k...)
+	}
+	kb = append(kb, 0)
+	devs := make([]C.int, 0, len(devices))
+	for _, d := range devices {
+		devs = append(devs, C.int(d))
+	}
+	var dp *C.int
+	nd := C.int(1)
+	if len(devs) > 0 {
+		dp, nd = &devs[0], C.int(len(devs))
+	}
+	flags := C.uint(0)
+	if prepare {
+		flags = C.BGLS_KEYS_PREPARE
+	}
+	var h C.bgls_keys_t
+	bad := C.size_t(len(keys))
+	if C.bgls_keys_upload_compressed(c.id, p(kb), C.size_t(len(keys)), dp, nd, flags, &h, &bad) != 0 {
+		if int(bad) < len(keys) {
+			return nil, int(bad)
+		}
+		return nil, -1
+	}
+	ks := &HipKeySet{c, h, len(keys)}
+	runtime.SetFinalizer(ks, func(k *HipKeySet) { C.bgls_keys_free(k.h) })
+	return ks, 0
+}
+
+// Keys reads the resident keys back as Points (bgls_keys_read); nil on failure.
+func (ks *HipKeySet) Keys() []Point {
+	gb := ks.c.size(C.BGLS_G2)
+	raw := make([]byte, ks.n*gb+1)
+	if C.bgls_keys_read(ks.h, 0, C.size_t(ks.n), p(raw)) != 0 {
+		return nil
+	}
+	out := make([]Point, ks.n)
+	for i := range out {
+		out[i] = &hipPoint{ks.c, C.BGLS_G2, append([]byte(nil), raw[i*gb:(i+1)*gb]...)}
+	}
+	return out
+}
+
 // VerifyAggregate is bgls.verifyAggSig (bgls/bgls.go:94-119) against the resident keys, on every GPU of the set.
 func (ks *HipKeySet) VerifyAggregate(aggsig Point, msgs [][]byte, allowDuplicates bool) bool {
 	s, ok := aggsig.(*hipPoint)

@@ -137,6 +137,29 @@ class KeySet {
   KeySet(const KeySet&) = delete;
   KeySet& operator=(const KeySet&) = delete;
   bool ok() const { return ok_; }
+  // A key set from compressed keys (Point.Marshal encodings, concatenated), decoded and validated on the device(s) in one pass as UnmarshalG2
+  // does (bgls_keys_upload_compressed).  !ok() where a key was refused; *first_bad then holds the smallest refused index.
+  static std::unique_ptr<KeySet> FromCompressed(const CurveSystem* curve, const Bytes& keys, const std::vector<int>& devices = {}, bool prepare = false,
+                                                size_t* first_bad = nullptr) {
+    std::unique_ptr<KeySet> ks(new KeySet(curve));
+    const size_t cb = bgls_g2_size(curve->id) / 2;
+    if (cb == 0 || keys.size() % cb) return ks;
+    ks->n_ = keys.size() / cb;
+    const int nd = devices.empty() ? 1 : (int)devices.size();
+    ks->ok_ = bgls_keys_upload_compressed(curve->id, keys.data(), ks->n_, devices.empty() ? nullptr : devices.data(), nd, prepare ? BGLS_KEYS_PREPARE : 0u, &ks->h_,
+                                          first_bad) == 0;
+    return ks;
+  }
+  // the resident keys as Points, read back from the device(s) (bgls_keys_read); empty on failure
+  std::vector<Point> Read() const {
+    std::vector<Point> out;
+    if (!ok_) return out;
+    const size_t gb = bgls_g2_size(curve_->id);
+    Bytes raw(n_ * gb + 1);
+    if (bgls_keys_read(h_, 0, n_, raw.data()) != 0) return out;
+    for (size_t i = 0; i < n_; ++i) out.push_back(Point{curve_, BGLS_G2, Bytes(raw.begin() + i * gb, raw.begin() + (i + 1) * gb)});
+    return out;
+  }
   // verifyAggSig (bgls/bgls.go:94-119) / verifyMultiSignature (bgls/bgls.go:89-92) against the resident keys
   bool VerifyAggregateSignature(const Point& aggsig, const std::vector<Bytes>& msgs, bool allowDuplicates = false) const {
     if (!ok_ || msgs.size() != n_ || aggsig.curve != curve_ || aggsig.group != BGLS_G1) return false;
@@ -275,6 +298,7 @@ class KeySet {
   }
 
  private:
+  explicit KeySet(const CurveSystem* curve) : curve_(curve), n_(0) {}       // FromCompressed fills it
   size_t stride() const { return n_ / 8 + 1; }             // at least ceil(n / 8), never 0
   // bitmap rows of the subsets (key i of a row: bit i & 7 of byte i >> 3); false on an index outside the set
   bool subset_rows(const std::vector<std::vector<size_t>>& subsets, Bytes& rows) const {

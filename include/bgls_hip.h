@@ -386,6 +386,11 @@ int bgls_compress_points(int curve, int group, const uint8_t* pts, size_t n, uin
  *     infinity flag with any other bit set, x >= p are refused), y = sqrt(x^3 + b) selected by the sort flag, then Check():
  *     membership in the order-r subgroup, G1 and G2 alike. */
 int bgls_decompress_points(int curve, int group, const uint8_t* in, size_t n, uint8_t* out, uint8_t* ok);
+/* The same decoding -- the same accepted set, the same bytes, G1 and G2, both curves -- over device-resident input, by the one-pass kernel
+ * on the carry-free limbs (wire_x.hpp / k_wirex.hip).  d_in: n compressed points, d_out: n uncompressed points (zeros where refused),
+ * d_ok: n bytes.  Asynchronous on `stream` (NULL: the calling thread's context stream), like the other _dev calls.  n == 0 returns 0
+ * without touching a pointer; a NULL pointer with n > 0, a bad group or n >= 2^30 is BGLS_ERR_ARG before any device work. */
+int bgls_decompress_points_dev(int curve, int group, const void* d_in, size_t n, void* d_out, void* d_ok, void* stream);
 
 /* ---- per-point operations backing the Go Point / PointT methods --------------------------- */
 /* Point.Add (curves/altbn128.go:59-66,181-188; curves/bls12_381.go:33-41,94-102) */
@@ -609,6 +614,17 @@ int bgls_keys_upload(int curve, const uint8_t* keys, size_t n, const int* device
  * are otherwise safe, each running on the calling thread's context. */
 int bgls_keys_free(bgls_keys_t handle);
 int bgls_keys_info(bgls_keys_t handle, int* curve, size_t* n, int* n_devices);
+/* A key set from n COMPRESSED G2 keys (Point.Marshal: 64 bytes on alt-bn128, 96 on BLS12-381).  Every shard uploads its range of the
+ * compressed bytes and decodes it on its device in one pass (UnmarshalG2: square root, sign rule, curve check, subgroup membership), so
+ * validation is always on: BGLS_KEYS_CHECK is implied and ignored, BGLS_KEYS_PREPARE acts as in bgls_keys_upload.  Any refused key fails
+ * the upload with BGLS_ERR_ENCODING, frees everything and, where first_bad is not NULL, writes the smallest refused index over all
+ * shards there; first_bad is left untouched on success and on every other error.  The set is the one bgls_keys_upload makes from the
+ * decompressed keys on the same devices with the same flags (keys at infinity included).  Devices and argument errors as there. */
+int bgls_keys_upload_compressed(int curve, const uint8_t* keys_c, size_t n, const int* devices, int n_devices, unsigned flags, bgls_keys_t* handle_out,
+                                size_t* first_bad);
+/* The uncompressed wire bytes of keys [first, first + count) of any key set, across its shards.  BGLS_ERR_ARG for an unknown handle, a
+ * range beyond the set, or a NULL out with count > 0. */
+int bgls_keys_read(bgls_keys_t handle, size_t first, size_t count, uint8_t* out);
 /* verifyAggSig (bgls/bgls.go:94-119) against a resident key set: message i belongs to key i; n must equal the set's size.
  * Every device of the set hashes its message range and multiplies its Miller values (one host thread per device), the
  * 384 / 576-byte partial products and status words meet on the first device (ncclAllGather over the devices' streams
