@@ -1,14 +1,15 @@
 """Host-side mirror of the reference's `bbsigs` package (bbsigs/bbsigs.go, bbsigs/hashedbbsigs.go): Boneh-Boyen signatures, same
 names and semantics.  Key generation and signing multiply a generator with bgls_scale_generator; verification is ONE
-bgls_bb_verify_batch call for the whole batch (a single Verify is a batch of one).  The scalar arithmetic of Sign (an inverse modulo
-the group order) and the blake2b-256 message hash of the hashed forms are host work, as in the reference."""
+bgls_bb_verify_batch call for the whole batch (a single Verify is a batch of one; _marshal.settle).  The scalar arithmetic of Sign (an
+inverse modulo the group order) and the blake2b-256 message hash of the hashed forms are host work, as in the reference."""
 import ctypes
 import hashlib
 import os
 import secrets
 from . import _lib
+from ._marshal import cat, is_point, mag32, scale_generator, settle
 from .bgls import _group_offsets
-from .curves import _reduce_scalar, Point, G1, G2
+from .curves import G1, G2
 
 
 class Privkey:                                      # bbsigs/bbsigs.go:13-17
@@ -32,25 +33,6 @@ class Signature:                                    # bbsigs/bbsigs.go:25-29
         self.Sigma, self.R = Sigma, R
 
 
-def _mag(curve, k):
-    """A scalar as the ABI's 32-byte magnitude: negative scalars and those of 2^256 and above are reduced modulo the group order
-    (as LoadPublicKeys does); every other value is passed unreduced."""
-    return _reduce_scalar(curve, k if k >= 0 else k % curve.GetG1Order()).to_bytes(32, "big")
-
-
-def _scale_generator(curve, group, scalars):
-    n = len(scalars)
-    if n == 0:
-        return []
-    size = len(curve.GetG1().raw) if group == G1 else len(curve.GetG2().raw)
-    o = _lib.out(n * size)
-    rc = _lib.load().bgls_scale_generator(curve.id, group, _lib.buf(b"".join(_mag(curve, k) for k in scalars)), n, o)
-    if rc != 0:
-        raise RuntimeError("bgls_scale_generator: %s" % _lib.last_error())
-    raw = bytes(o)
-    return [Point(curve, group, raw[i * size:(i + 1) * size]) for i in range(n)]
-
-
 def KeyGen(curve):                                  # bbsigs/bbsigs.go:31-39
     order = curve.GetG1Order()
     x, y = secrets.randbelow(order), secrets.randbelow(order)
@@ -58,7 +40,7 @@ def KeyGen(curve):                                  # bbsigs/bbsigs.go:31-39
 
 
 def LoadPublicKey(curve, x, y):                     # bbsigs/bbsigs.go:41-45
-    u, v = _scale_generator(curve, G2, [x, y])
+    u, v = scale_generator(curve, G2, [x, y])
     return Pubkey(u, v)
 
 
@@ -88,37 +70,33 @@ def SignBatch(curve, sks, msgs):
         r, e = _sign_exponent(curve, sk, m)
         rs.append(r)
         es.append(e)
-    return [Signature(s, r) for s, r in zip(_scale_generator(curve, G1, es), rs)]
+    return [Signature(s, r) for s, r in zip(scale_generator(curve, G1, es), rs)]
 
 
 def _batchable(curve, sig, pk):
-    return (isinstance(sig, Signature) and isinstance(pk, Pubkey) and isinstance(sig.Sigma, Point) and sig.Sigma.curve is curve
-            and sig.Sigma.group == G1 and all(isinstance(p, Point) and p.curve is curve and p.group == G2 for p in (pk.U, pk.V)))
+    return (isinstance(sig, Signature) and isinstance(pk, Pubkey) and is_point(sig.Sigma, curve, G1)
+            and is_point(pk.U, curve, G2) and is_point(pk.V, curve, G2))
+
+
+def _items(curve, sigs, pks, msgs):
+    """the four blobs of bgls_bb_verify_batch and its combined form: sigmas, the magnitudes of r, U || V per key, the magnitudes of m"""
+    return (cat(s.Sigma for s in sigs), _lib.buf(b"".join(mag32(curve, s.R) for s in sigs)),
+            _lib.buf(b"".join(k.U.raw + k.V.raw for k in pks)), _lib.buf(b"".join(mag32(curve, m) for m in msgs)))
 
 
 def _verify_batch(curve, sigs, pks, msgs):
     """One bgls_bb_verify_batch call for the items made of this curve's Points (any other item is rejected, as a mismatched
-    Add / Pair in the reference yields a result that never equals GetGT()).  A call that fails as a whole (an encoding error
-    somewhere in the batch) is settled item by item."""
+    Add / Pair in the reference yields a result that never equals GetGT()); _marshal.settle."""
     if not (len(sigs) == len(pks) == len(msgs)):
         raise ValueError("sigs, pks and msgs differ in length")
-    out = [False] * len(sigs)
-    batch = [b for b in range(len(sigs)) if _batchable(curve, sigs[b], pks[b])]
-    if not batch:
-        return out
-    n = len(batch)
-    verdicts = (ctypes.c_uint8 * n)()
-    rc = _lib.load().bgls_bb_verify_batch(curve.id, _lib.buf(b"".join(sigs[b].Sigma.raw for b in batch)),
-                                          _lib.buf(b"".join(_mag(curve, sigs[b].R) for b in batch)),
-                                          _lib.buf(b"".join(pks[b].U.raw + pks[b].V.raw for b in batch)),
-                                          _lib.buf(b"".join(_mag(curve, msgs[b]) for b in batch)), n, verdicts, None)
-    if rc < 0 and n > 1:
-        for b in batch:
-            out[b] = _verify_batch(curve, [sigs[b]], [pks[b]], [msgs[b]])[0]
-        return out
-    for i, b in enumerate(batch):
-        out[b] = rc >= 0 and verdicts[i] == 1
-    return out
+
+    def call(items):
+        verdicts = _lib.out(len(items))
+        rc = _lib.load().bgls_bb_verify_batch(curve.id, *_items(curve, [sigs[b] for b in items], [pks[b] for b in items], [msgs[b] for b in items]),
+                                              len(items), verdicts, None)
+        return rc, verdicts
+
+    return settle(len(sigs), lambda b: _batchable(curve, sigs[b], pks[b]), call)
 
 
 def Verify(curve, sig, pk, msg):                    # bbsigs/bbsigs.go:68-73
@@ -149,12 +127,9 @@ def VerifyBatchCombined(curve, sigs, pks, msgs, group=None, seed=None):
     if not all(_batchable(curve, s, k) for s, k in zip(sigs, pks)):
         raise ValueError("the combined check takes Signatures and Pubkeys made of G1 / G2 Points of this curve only")
     goff = _group_offsets(n, group)
-    verdicts = (ctypes.c_uint8 * (len(goff) - 1))()
-    rc = _lib.load().bgls_bb_verify_batch_combined(curve.id, _lib.buf(b"".join(s.Sigma.raw for s in sigs)),
-                                                   _lib.buf(b"".join(_mag(curve, s.R) for s in sigs)),
-                                                   _lib.buf(b"".join(k.U.raw + k.V.raw for k in pks)),
-                                                   _lib.buf(b"".join(_mag(curve, m) for m in msgs)), n,
-                                                   (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1, _lib.buf(bytes(seed)), verdicts, None)
+    verdicts = _lib.out(len(goff) - 1)
+    rc = _lib.load().bgls_bb_verify_batch_combined(curve.id, *_items(curve, sigs, pks, msgs), n, (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1,
+                                                   _lib.buf(bytes(seed)), verdicts, None)
     if rc < 0:
         raise ValueError("bgls_bb_verify_batch_combined: %s" % _lib.last_error())
     return [v == 1 for v in verdicts]

@@ -1,10 +1,12 @@
 """Host-side mirror of the reference's `bgls` scheme functions on the hot path
-(bgls/bgls.go, bgls/blsKosk.go), same names and semantics, each routed to ONE batch C call."""
+(bgls/bgls.go, bgls/blsKosk.go), same names and semantics, each routed to ONE batch C call.  The calls that return one verdict per
+item are a predicate, a closure that marshals a list of items, and _marshal.settle, which states the batch-and-settle rule once."""
 import ctypes
 import os
 import secrets
 from . import _lib
-from .curves import _reduce_scalar, AggregatePoints, ScalePoints, Point, G1, G2
+from ._marshal import all_points, cat, is_point, mag32, msgs_arg, prefix_u64, scale_generator, settle, split_points
+from .curves import AggregatePoints, ScalePoints, Point, G1, G2
 
 
 def KeyGen(curve):                                   # bgls/bgls.go:30-37
@@ -20,8 +22,16 @@ def Sign(curve, sk, msg):                            # bgls/bgls.go:46-56
     return curve.HashToG1(msg).Mul(sk)
 
 
+def _kosk1(msg):                                     # the proof-of-possession schemes sign and verify 0x01 || msg (bgls/blsKosk.go:73-77)
+    return b"\x01" + bytes(msg)
+
+
+def _kosk(msgs):
+    return [_kosk1(m) for m in msgs]
+
+
 def KoskSign(curve, sk, msg):                        # bgls/blsKosk.go:73-77
-    return Sign(curve, sk, b"\x01" + bytes(msg))
+    return Sign(curve, sk, _kosk1(msg))
 
 
 def AggregateSignatures(sigs):                       # bgls/bgls.go:123-125
@@ -41,12 +51,9 @@ class KeySet:
         raw = b"".join(k.raw for k in keys) if keys and isinstance(keys[0], Point) else bytes(keys)
         n = len(raw) // (4 * curve.fp_bytes)
         h = ctypes.c_uint64()
-        if devices:
-            devs = list(devices)
-            rc = _lib.load().bgls_keys_upload(curve.id, _lib.buf(raw), n, (ctypes.c_int * len(devs))(*devs), len(devs), 1 if check else 0,
-                                              ctypes.byref(h))
-        else:                                         # NULL + one shard: the process' default device (bgls_init / bgls_select_device), as in the C++ and Go mirrors
-            rc = _lib.load().bgls_keys_upload(curve.id, _lib.buf(raw), n, None, 1, 1 if check else 0, ctypes.byref(h))
+        devs = list(devices) if devices else None     # NULL + one shard: the process' default device (bgls_init / bgls_select_device), as in the C++ and Go mirrors
+        rc = _lib.load().bgls_keys_upload(curve.id, _lib.buf(raw), n, (ctypes.c_int * len(devs))(*devs) if devs else None, len(devs) if devs else 1,
+                                          1 if check else 0, ctypes.byref(h))
         if rc != 0:
             raise ValueError("bgls_keys_upload: %d %s" % (rc, _lib.last_error()))
         self.curve, self.n, self.handle = curve, n, h.value
@@ -74,13 +81,11 @@ class KeySet:
 
     def keys(self):
         """the set's keys as Points, read back from the device(s) (bgls_keys_read)"""
-        gb = 4 * self.curve.fp_bytes
-        out = (ctypes.c_uint8 * max(1, self.n * gb))()
+        out = _lib.out(self.n * 4 * self.curve.fp_bytes)
         rc = _lib.load().bgls_keys_read(self.handle, 0, self.n, out)
         if rc != 0:
             raise ValueError("bgls_keys_read: %d %s" % (rc, _lib.last_error()))
-        raw = bytes(out)
-        return [Point(self.curve, G2, raw[i * gb:(i + 1) * gb]) for i in range(self.n)]
+        return split_points(self.curve, G2, bytes(out), self.n)
 
     def __len__(self):
         return self.n
@@ -97,33 +102,20 @@ class KeySet:
             pass
 
 
-def _offsets(msgs):
-    off = (ctypes.c_uint64 * (len(msgs) + 1))()
-    acc = 0
-    for i, m in enumerate(msgs):
-        off[i] = acc
-        acc += len(m)
-    off[len(msgs)] = acc
-    return off
-
-
 def _verify_agg(curve, aggsig, keys, msgs, allow_duplicates):
     if len(keys) != len(msgs):                       # bgls/bgls.go:95-97
         return False
-    n = len(keys)
-    if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+    if not is_point(aggsig, curve, G1):
         return False
     if isinstance(keys, KeySet):
         if keys.curve is not curve:
             return False
-        return _lib.load().bgls_verify_aggregate_h(keys.handle, _lib.buf(aggsig.raw), _lib.buf(b"".join(bytes(m) for m in msgs)),
-                                                   _offsets(msgs), n, 1 if allow_duplicates else 0) == 1
-    for k in keys:
-        if not (isinstance(k, Point) and k.curve is curve and k.group == G2):
-            return False
-    off = _offsets(msgs)
-    rc = _lib.load().bgls_verify_aggregate(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)),
-                                           _lib.buf(b"".join(bytes(m) for m in msgs)), off, n, 1 if allow_duplicates else 0)
+        return _lib.load().bgls_verify_aggregate_h(keys.handle, _lib.buf(aggsig.raw), *msgs_arg([bytes(m) for m in msgs]), len(msgs),
+                                                   1 if allow_duplicates else 0) == 1
+    if not all_points(keys, curve, G2):
+        return False
+    rc = _lib.load().bgls_verify_aggregate(curve.id, _lib.buf(aggsig.raw), cat(keys), *msgs_arg([bytes(m) for m in msgs]), len(msgs),
+                                           1 if allow_duplicates else 0)
     return rc == 1                                   # every failure collapses to false (bgls.go:115-118)
 
 
@@ -132,7 +124,7 @@ def VerifyAggregateSignature(curve, aggsig, keys, msgs):      # bgls/bgls.go:82-
 
 
 def KoskVerifyAggregateSignature(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:100-106
-    return _verify_agg(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs], True)
+    return _verify_agg(curve, aggsig, keys, _kosk(msgs), True)
 
 
 def GroupMessages(msgs):
@@ -142,7 +134,7 @@ def GroupMessages(msgs):
     n = len(ms)
     group_of = (ctypes.c_uint32 * max(n, 1))()
     n_groups = ctypes.c_size_t(0)
-    rc = _lib.load().bgls_group_messages(_lib.buf(b"".join(ms)), _offsets(ms), n, group_of, ctypes.byref(n_groups))
+    rc = _lib.load().bgls_group_messages(*msgs_arg(ms), n, group_of, ctypes.byref(n_groups))
     if rc != 0:
         raise RuntimeError("bgls_group_messages: %d %s" % (rc, _lib.last_error()))
     return list(group_of)[:n], n_groups.value
@@ -159,19 +151,14 @@ def VerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):
                         "(or the signer-bitmap calls VerifyMultiSignaturesBySubset / AggregateKeysBySubset)")
     if len(keys) != len(msgs):                       # bgls/bgls.go:95-97
         return False
-    if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+    if not (is_point(aggsig, curve, G1) and all_points(keys, curve, G2)):
         return False
-    for k in keys:
-        if not (isinstance(k, Point) and k.curve is curve and k.group == G2):
-            return False
-    ms = [bytes(m) for m in msgs]
-    rc = _lib.load().bgls_verify_aggregate_grouped(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), _lib.buf(b"".join(ms)),
-                                                   _offsets(ms), len(ms), None, None)
+    rc = _lib.load().bgls_verify_aggregate_grouped(curve.id, _lib.buf(aggsig.raw), cat(keys), *msgs_arg([bytes(m) for m in msgs]), len(msgs), None, None)
     return rc == 1                                   # every failure collapses to false (bgls.go:115-118)
 
 
 def KoskVerifyAggregateSignatureGrouped(curve, aggsig, keys, msgs):  # bgls/blsKosk.go:100-106
-    return VerifyAggregateSignatureGrouped(curve, aggsig, keys, [b"\x01" + bytes(m) for m in msgs])
+    return VerifyAggregateSignatureGrouped(curve, aggsig, keys, _kosk(msgs))
 
 
 def VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, msgs):
@@ -198,44 +185,44 @@ def VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, msgs)
         order = sorted(range(len(idx)), key=lambda j: idx[j])
         ms = [ms[j] for j in order]
         bitmap = _subset_rows(keyset, [idx])[0]
-    if keyset.curve is not curve or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+    if keyset.curve is not curve or not is_point(aggsig, curve, G1):
         return False
     rc = _lib.load().bgls_verify_aggregate_grouped_h(keyset.handle, _lib.buf(aggsig.raw), None if bitmap is None else _lib.buf(bitmap),
-                                                     0 if bitmap is None else len(bitmap), _lib.buf(b"".join(ms)), _offsets(ms), len(ms), None, None)
+                                                     0 if bitmap is None else len(bitmap), *msgs_arg(ms), len(ms), None, None)
     return rc == 1
 
 
 def KoskVerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, msgs):  # bgls/blsKosk.go:100-106
-    return VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, [b"\x01" + bytes(m) for m in msgs])
+    return VerifyAggregateSignatureGroupedBySubset(curve, aggsig, keyset, subset, _kosk(msgs))
+
+
+def _set_ok(curve, sig, keys):
+    """a G1 signature and a list of G2 keys of this curve: what the batch entries over sets of keys take"""
+    return is_point(sig, curve, G1) and not isinstance(keys, KeySet) and all_points(keys, curve, G2)
+
+
+def _sets_call(entry, curve, sigs, keys, msgs, before=(), after=(None,)):
+    """settle()'s call(items) for the batch entries over sets of keys (bgls_verify_aggregate_batch, _distinct_batch, bgls_verify_multi_sets,
+    _hae_sets): the signatures, the keys keys[b] and the messages msgs[b] (a list) of the items in order, key_off / inst_off counting
+    keys; before / after: what the entry takes around `verdicts`."""
+    def call(items):
+        verdicts = _lib.out(len(items))
+        rc = getattr(_lib.load(), entry)(curve.id, cat(sigs[b] for b in items), cat(k for b in items for k in keys[b]),
+                                         prefix_u64(len(keys[b]) for b in items), len(items),
+                                         *msgs_arg([bytes(m) for b in items for m in msgs[b]]), *before, verdicts, *after)
+        return rc, verdicts
+    return call
 
 
 def _verify_agg_batch(curve, aggsigs, keys_per_instance, msgs_per_instance, allow_duplicates):
     """One bgls_verify_aggregate_batch call for every instance made of Points of this curve; an instance that is not (mismatched lengths,
-    a foreign point, a KeySet) gets what _verify_agg says about it alone.  A call that fails as a whole (an encoding or hashing error
-    somewhere in the batch) is settled instance by instance, so that the list equals the single calls' results."""
+    a foreign point, a KeySet) gets what _verify_agg says about it alone (_marshal.settle)."""
     if not (len(aggsigs) == len(keys_per_instance) == len(msgs_per_instance)):
         raise ValueError("aggsigs, keys_per_instance and msgs_per_instance differ in length")
-    out = [False] * len(aggsigs)
-    batch = []
-    for b, (sig, keys, msgs) in enumerate(zip(aggsigs, keys_per_instance, msgs_per_instance)):
-        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet) and len(keys) == len(msgs)
-                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
-            batch.append(b)
-        else:
-            out[b] = _verify_agg(curve, sig, keys, msgs, allow_duplicates)
-    if not batch:
-        return out
-    inst_off = (ctypes.c_uint64 * (len(batch) + 1))()
-    for i, b in enumerate(batch):
-        inst_off[i + 1] = inst_off[i] + len(keys_per_instance[b])
-    msgs = [bytes(m) for b in batch for m in msgs_per_instance[b]]
-    verdicts = (ctypes.c_uint8 * len(batch))()
-    rc = _lib.load().bgls_verify_aggregate_batch(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
-                                                 _lib.buf(b"".join(k.raw for b in batch for k in keys_per_instance[b])), inst_off, len(batch),
-                                                 _lib.buf(b"".join(msgs)), _offsets(msgs), 1 if allow_duplicates else 0, verdicts, None)
-    for i, b in enumerate(batch):
-        out[b] = verdicts[i] == 1 if rc >= 0 else _verify_agg(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b], allow_duplicates)
-    return out
+    return settle(len(aggsigs),
+                  lambda b: _set_ok(curve, aggsigs[b], keys_per_instance[b]) and len(keys_per_instance[b]) == len(msgs_per_instance[b]),
+                  _sets_call("bgls_verify_aggregate_batch", curve, aggsigs, keys_per_instance, msgs_per_instance, before=(1 if allow_duplicates else 0,)),
+                  lambda b: _verify_agg(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b], allow_duplicates))
 
 
 def VerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
@@ -245,21 +232,19 @@ def VerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instan
 
 def KoskVerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
     """The batch of KoskVerifyAggregateSignature calls (bgls/blsKosk.go:100-106): 0x01 prepended to every message, duplicates allowed."""
-    return _verify_agg_batch(curve, aggsigs, keys_per_instance, [[b"\x01" + bytes(m) for m in ms] for ms in msgs_per_instance], True)
+    return _verify_agg_batch(curve, aggsigs, keys_per_instance, [_kosk(ms) for ms in msgs_per_instance], True)
 
 
 def _verify_multi(curve, aggsig, keys, msg):                  # bgls/bgls.go:89-92
+    if not is_point(aggsig, curve, G1):
+        return False                                 # a nil / foreign aggsig is `false`, never an exception
     if isinstance(keys, KeySet):
-        if keys.curve is not curve or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+        if keys.curve is not curve:
             return False
         return _lib.load().bgls_verify_multi_h(keys.handle, _lib.buf(aggsig.raw), _lib.buf(msg), len(msg)) == 1
-    if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
-        return False                                 # a nil / foreign aggsig is `false`, never an exception
-    for k in keys:
-        if not (isinstance(k, Point) and k.curve is curve and k.group == G2):
-            return False
-    rc = _lib.load().bgls_verify_multi(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), len(keys),
-                                       _lib.buf(msg), len(msg))
+    if not all_points(keys, curve, G2):
+        return False
+    rc = _lib.load().bgls_verify_multi(curve.id, _lib.buf(aggsig.raw), cat(keys), len(keys), _lib.buf(msg), len(msg))
     return rc == 1
 
 
@@ -268,40 +253,21 @@ def VerifySingleSignature(curve, sig, pubkey, msg):           # bgls/bgls.go:59-
 
 
 def KoskVerifySingleSignature(curve, sig, pubkey, msg):       # bgls/blsKosk.go:86-90
-    return VerifySingleSignature(curve, sig, pubkey, b"\x01" + bytes(msg))
+    return VerifySingleSignature(curve, sig, pubkey, _kosk1(msg))
 
 
 def KoskVerifyMultiSignature(curve, aggsig, keys, msg):       # bgls/blsKosk.go:117-120
-    return _verify_multi(curve, aggsig, keys, b"\x01" + bytes(msg))
+    return _verify_multi(curve, aggsig, keys, _kosk1(msg))
 
 
 def _verify_multi_sets(curve, aggsigs, keys_per_set, msgs):
     """One bgls_verify_multi_sets call for every set made of Points of this curve; a set that is not (a nil or foreign signature, a
-    foreign key, a KeySet) gets what _verify_multi says about it alone.  A call that fails as a whole (an encoding or hashing error
-    somewhere in the batch) is settled set by set, so that the list equals the single calls' results."""
+    foreign key, a KeySet) gets what _verify_multi says about it alone (_marshal.settle)."""
     if not (len(aggsigs) == len(keys_per_set) == len(msgs)):
         raise ValueError("aggsigs, keys_per_set and msgs differ in length")
-    out = [False] * len(aggsigs)
-    batch = []
-    for b, (sig, keys) in enumerate(zip(aggsigs, keys_per_set)):
-        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet)
-                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
-            batch.append(b)
-        else:
-            out[b] = _verify_multi(curve, sig, keys, bytes(msgs[b]))
-    if not batch:
-        return out
-    key_off = (ctypes.c_uint64 * (len(batch) + 1))()
-    for i, b in enumerate(batch):
-        key_off[i + 1] = key_off[i] + len(keys_per_set[b])
-    ms = [bytes(msgs[b]) for b in batch]
-    verdicts = (ctypes.c_uint8 * len(batch))()
-    rc = _lib.load().bgls_verify_multi_sets(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
-                                            _lib.buf(b"".join(k.raw for b in batch for k in keys_per_set[b])), key_off, len(batch),
-                                            _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None)
-    for i, b in enumerate(batch):
-        out[b] = verdicts[i] == 1 if rc >= 0 else _verify_multi(curve, aggsigs[b], keys_per_set[b], ms[i])
-    return out
+    return settle(len(aggsigs), lambda b: _set_ok(curve, aggsigs[b], keys_per_set[b]),
+                  _sets_call("bgls_verify_multi_sets", curve, aggsigs, keys_per_set, [[m] for m in msgs]),
+                  lambda b: _verify_multi(curve, aggsigs[b], keys_per_set[b], bytes(msgs[b])))
 
 
 def VerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
@@ -312,7 +278,7 @@ def VerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
 def KoskVerifyMultiSignatures(curve, aggsigs, pubkeys, msgs):
     """len(aggsigs) independent KoskVerifyMultiSignature calls (bgls/blsKosk.go:117-120) in one batch: 0x01 prepended to every message,
     a list of bools, one per set (pubkeys[b]: the signers of msgs[b])."""
-    return _verify_multi_sets(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
+    return _verify_multi_sets(curve, aggsigs, pubkeys, _kosk(msgs))
 
 
 def _subset_rows(keyset, subsets):
@@ -344,52 +310,38 @@ def AggregateKeysBySubset(keyset, subsets):
         return []
     curve = keyset.curve
     rows, stride = _subset_rows(keyset, subsets)
-    out = (ctypes.c_uint8 * (len(subsets) * 4 * curve.fp_bytes))()
+    out = _lib.out(len(subsets) * 4 * curve.fp_bytes)
     rc = _lib.load().bgls_aggregate_subsets_h(keyset.handle, _lib.buf(rows), stride, len(subsets), out)
     if rc != 0:
         raise ValueError("bgls_aggregate_subsets_h: %d %s" % (rc, _lib.last_error()))
-    raw = bytes(out)
-    return [Point(curve, G2, raw[b * 4 * curve.fp_bytes:(b + 1) * 4 * curve.fp_bytes]) for b in range(len(subsets))]
+    return split_points(curve, G2, bytes(out), len(subsets))
 
 
 def VerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, msgs):
     """len(aggsigs) independent verifyMultiSignature calls (bgls/bgls.go:89-92) whose signers are sub-slices of ONE resident KeySet -- a
     MultiSig{keys, sig, msg} over registered keys is one row -- in one bgls_verify_multi_subsets_h call: a list of bools, one per set.  A
     nil or foreign signature is False without a call; a call that fails as a whole (an off-curve signature, an exhausted hash) is settled
-    set by set, so that the list equals the single calls' results."""
+    set by set through calls of one row (_marshal.settle)."""
     if not isinstance(keyset, KeySet):
         raise TypeError("VerifyMultiSignaturesBySubset takes a KeySet")
     if not (len(aggsigs) == len(subsets) == len(msgs)):
         raise ValueError("aggsigs, subsets and msgs differ in length")
-    out = [False] * len(aggsigs)
     if keyset.curve is not curve:
-        return out
-    batch = [b for b, s in enumerate(aggsigs) if isinstance(s, Point) and s.curve is curve and s.group == G1]
-    if not batch:
-        return out
-    rows, stride = _subset_rows(keyset, [subsets[b] for b in batch])
-    ms = [bytes(msgs[b]) for b in batch]
+        return [False] * len(aggsigs)
 
-    def call(idx):
-        verdicts = (ctypes.c_uint8 * len(idx))()
-        rc = _lib.load().bgls_verify_multi_subsets_h(keyset.handle, _lib.buf(b"".join(aggsigs[batch[i]].raw for i in idx)),
-                                                     _lib.buf(b"".join(rows[i * stride:(i + 1) * stride] for i in idx)), stride, len(idx),
-                                                     _lib.buf(b"".join(ms[i] for i in idx)), _offsets([ms[i] for i in idx]), verdicts, None, None)
+    def call(items):
+        rows, stride = _subset_rows(keyset, [subsets[b] for b in items])
+        verdicts = _lib.out(len(items))
+        rc = _lib.load().bgls_verify_multi_subsets_h(keyset.handle, cat(aggsigs[b] for b in items), _lib.buf(rows), stride, len(items),
+                                                     *msgs_arg([bytes(msgs[b]) for b in items]), verdicts, None, None)
         return rc, verdicts
 
-    rc, verdicts = call(list(range(len(batch))))
-    for i, b in enumerate(batch):
-        if rc >= 0:
-            out[b] = verdicts[i] == 1
-        else:
-            rc1, v1 = call([i])
-            out[b] = rc1 >= 0 and v1[0] == 1
-    return out
+    return settle(len(aggsigs), lambda b: is_point(aggsigs[b], curve, G1), call)
 
 
 def KoskVerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, msgs):
     """The same for KoskVerifyMultiSignature (bgls/blsKosk.go:117-120): 0x01 prepended to every message."""
-    return VerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, [b"\x01" + bytes(m) for m in msgs])
+    return VerifyMultiSignaturesBySubset(curve, aggsigs, keyset, subsets, _kosk(msgs))
 
 
 def _group_offsets(n, group):
@@ -416,19 +368,13 @@ def VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group=None, see
         raise ValueError("seed must be 32 bytes")
     if n == 0:
         return []
-    for sig, keys in zip(aggsigs, pubkeys):
-        if not (isinstance(sig, Point) and sig.curve is curve and sig.group == G1
-                and all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)):
-            raise ValueError("the combined check takes G1 / G2 Points of this curve only")
+    if not all(is_point(sig, curve, G1) and all_points(keys, curve, G2) for sig, keys in zip(aggsigs, pubkeys)):
+        raise ValueError("the combined check takes G1 / G2 Points of this curve only")
     goff = _group_offsets(n, group)
-    key_off = (ctypes.c_uint64 * (n + 1))()
-    for b in range(n):
-        key_off[b + 1] = key_off[b] + len(pubkeys[b])
-    ms = [bytes(m) for m in msgs]
-    verdicts = (ctypes.c_uint8 * (len(goff) - 1))()
-    rc = _lib.load().bgls_verify_multi_sets_combined(curve.id, _lib.buf(b"".join(s.raw for s in aggsigs)),
-                                                     _lib.buf(b"".join(k.raw for keys in pubkeys for k in keys)), key_off, n, _lib.buf(b"".join(ms)),
-                                                     _offsets(ms), (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1, _lib.buf(bytes(seed)), verdicts, None)
+    verdicts = _lib.out(len(goff) - 1)
+    rc = _lib.load().bgls_verify_multi_sets_combined(curve.id, cat(aggsigs), cat(k for keys in pubkeys for k in keys),
+                                                     prefix_u64(len(keys) for keys in pubkeys), n, *msgs_arg([bytes(m) for m in msgs]),
+                                                     (ctypes.c_uint64 * len(goff))(*goff), len(goff) - 1, _lib.buf(bytes(seed)), verdicts, None)
     if rc < 0:
         raise ValueError("bgls_verify_multi_sets_combined: %s" % _lib.last_error())
     return [v == 1 for v in verdicts]
@@ -436,7 +382,7 @@ def VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group=None, see
 
 def KoskVerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, msgs, group=None, seed=None):
     """VerifyMultiSignaturesCombined with 0x01 prepended to every message (bgls/blsKosk.go:117-120)."""
-    return VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, [b"\x01" + bytes(m) for m in msgs], group, seed)
+    return VerifyMultiSignaturesCombined(curve, aggsigs, pubkeys, _kosk(msgs), group, seed)
 
 
 def VerifyMultiSignaturesLocated(curve, aggsigs, pubkeys, msgs, group=64, seed=None):
@@ -460,7 +406,7 @@ def VerifySingleSignatures(curve, sigs, pubkeys, msgs):
 
 def KoskVerifySingleSignatures(curve, sigs, pubkeys, msgs):
     """The batch of KoskVerifySingleSignature calls (bgls/blsKosk.go:86-90): 0x01 prepended to every message."""
-    return VerifySingleSignatures(curve, sigs, pubkeys, [b"\x01" + bytes(m) for m in msgs])
+    return VerifySingleSignatures(curve, sigs, pubkeys, _kosk(msgs))
 
 
 def KoskVerifyBatchMultiSignature(curve, aggsigs, pubkeys, msgs):      # bgls/blsKosk.go:126-133
@@ -469,19 +415,10 @@ def KoskVerifyBatchMultiSignature(curve, aggsigs, pubkeys, msgs):      # bgls/bl
     AggregateKeys, KoskVerifyAggregateSignature)."""
     if len(aggsigs) != len(pubkeys) or len(pubkeys) != len(msgs) or not msgs:
         return False
-    if any(s.curve is not curve or s.group != G1 for s in aggsigs):
+    if not (all_points(aggsigs, curve, G1) and all(all_points(ks, curve, G2) for ks in pubkeys)):
         return False
-    if any(k.curve is not curve or k.group != G2 for ks in pubkeys for k in ks):
-        return False
-    koff = (ctypes.c_uint64 * (len(pubkeys) + 1))()
-    for i, ks in enumerate(pubkeys):
-        koff[i + 1] = koff[i] + len(ks)
-    pm = [b"\x01" + bytes(m) for m in msgs]
-    moff = (ctypes.c_uint64 * (len(pm) + 1))()
-    for i, m in enumerate(pm):
-        moff[i + 1] = moff[i] + len(m)
-    rc = _lib.load().bgls_verify_multi_batch(curve.id, _lib.buf(b"".join(s.raw for s in aggsigs)), _lib.buf(b"".join(k.raw for ks in pubkeys for k in ks)),
-                                             koff, len(msgs), _lib.buf(b"".join(pm)), moff, 1)
+    rc = _lib.load().bgls_verify_multi_batch(curve.id, cat(aggsigs), cat(k for ks in pubkeys for k in ks), prefix_u64(len(ks) for ks in pubkeys),
+                                             len(msgs), *msgs_arg(_kosk(msgs)), 1)
     return rc == 1
 
 
@@ -502,18 +439,14 @@ class MultiSig:                                               # bgls/bgls.go:15-
 
 
 # ---- hashed aggregation exponents (bgls/blsHAE.go) -----------------------------------------------------------
-def _g2_keys_ok(curve, keys):
-    return all(isinstance(k, Point) and k.curve is curve and k.group == G2 for k in keys)
-
-
 def hashPubKeysToExponents(pubkeys):                          # bgls/blsHAE.go:80-93
     if not pubkeys:
         return []
-    curve = pubkeys[0].curve if isinstance(pubkeys[0], Point) else None
-    if curve is None or not _g2_keys_ok(curve, pubkeys):      # the C side reads n * g2_size bytes: G2 points of ONE curve only
+    curve = getattr(pubkeys[0], "curve", None)
+    if curve is None or not all_points(pubkeys, curve, G2):   # the C side reads n * g2_size bytes: G2 points of ONE curve only
         raise TypeError("hashPubKeysToExponents takes G2 public keys of one curve")
     o = _lib.out(16 * len(pubkeys))
-    rc = _lib.load().bgls_hae_exponents(curve.id, _lib.buf(b"".join(k.raw for k in pubkeys)), len(pubkeys), o)
+    rc = _lib.load().bgls_hae_exponents(curve.id, cat(pubkeys), len(pubkeys), o)
     if rc != 0:
         raise RuntimeError("bgls_hae_exponents: %s" % _lib.last_error())
     raw = bytes(o)
@@ -526,66 +459,36 @@ def AggregateSignaturesWithHAE(sigs, pubkeys):                # bgls/blsHAE.go:3
     if not sigs:
         return AggregatePoints(sigs)
     curve = sigs[0].curve
-    if not _g2_keys_ok(curve, pubkeys) or not all(isinstance(s, Point) and s.curve is curve and s.group == G1 for s in sigs):
+    if not (all_points(pubkeys, curve, G2) and all_points(sigs, curve, G1)):
         return None
     o = _lib.out(len(sigs[0].raw))
-    rc = _lib.load().bgls_aggregate_signatures_hae(curve.id, _lib.buf(b"".join(s.raw for s in sigs)),
-                                                   _lib.buf(b"".join(k.raw for k in pubkeys)), len(sigs), o)
+    rc = _lib.load().bgls_aggregate_signatures_hae(curve.id, cat(sigs), cat(pubkeys), len(sigs), o)
     return Point(curve, G1, bytes(o)) if rc == 0 else None
 
 
 def VerifyAggregateSignatureWithHAE(curve, aggsig, pubkeys, msgs):   # bgls/blsHAE.go:49-53
-    if len(pubkeys) != len(msgs) or not _g2_keys_ok(curve, pubkeys):
+    if len(pubkeys) != len(msgs) or not all_points(pubkeys, curve, G2) or not is_point(aggsig, curve, G1):
         return False
-    if not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
-        return False
-    n = len(pubkeys)
-    off = (ctypes.c_uint64 * (n + 1))()
-    acc = 0
-    for i, m in enumerate(msgs):
-        off[i] = acc
-        acc += len(m)
-    off[n] = acc
-    rc = _lib.load().bgls_verify_aggregate_hae(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in pubkeys)),
-                                               _lib.buf(b"".join(bytes(m) for m in msgs)), off, n)
+    rc = _lib.load().bgls_verify_aggregate_hae(curve.id, _lib.buf(aggsig.raw), cat(pubkeys), *msgs_arg([bytes(m) for m in msgs]), len(msgs))
     return rc == 1
 
 
 def VerifyMultiSignatureWithHAE(curve, aggsig, pubkeys, msg):        # bgls/blsHAE.go:56-58
-    if not _g2_keys_ok(curve, pubkeys) or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+    if not all_points(pubkeys, curve, G2) or not is_point(aggsig, curve, G1):
         return False
-    rc = _lib.load().bgls_verify_multi_hae(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in pubkeys)), len(pubkeys),
-                                           _lib.buf(msg), len(msg))
+    rc = _lib.load().bgls_verify_multi_hae(curve.id, _lib.buf(aggsig.raw), cat(pubkeys), len(pubkeys), _lib.buf(msg), len(msg))
     return rc == 1
 
 
 def VerifyMultiSignaturesWithHAE(curve, aggsigs, pubkeys, msgs):
     """len(aggsigs) independent VerifyMultiSignatureWithHAE calls (bgls/blsHAE.go:56-58) in one bgls_verify_multi_hae_sets call: a list
     of bools, one per set.  A set that is not made of Points of this curve (a nil or foreign signature, a foreign key, a KeySet) gets
-    what VerifyMultiSignatureWithHAE says about it alone; a call that fails as a whole is settled set by set."""
+    what VerifyMultiSignatureWithHAE says about it alone (_marshal.settle)."""
     if not (len(aggsigs) == len(pubkeys) == len(msgs)):
         raise ValueError("aggsigs, pubkeys and msgs differ in length")
-    out = [False] * len(aggsigs)
-    batch = []
-    for b, (sig, keys) in enumerate(zip(aggsigs, pubkeys)):
-        if (isinstance(sig, Point) and sig.curve is curve and sig.group == G1 and not isinstance(keys, KeySet)
-                and _g2_keys_ok(curve, keys)):
-            batch.append(b)
-        else:
-            out[b] = VerifyMultiSignatureWithHAE(curve, sig, keys, bytes(msgs[b]))
-    if not batch:
-        return out
-    key_off = (ctypes.c_uint64 * (len(batch) + 1))()
-    for i, b in enumerate(batch):
-        key_off[i + 1] = key_off[i] + len(pubkeys[b])
-    ms = [bytes(msgs[b]) for b in batch]
-    verdicts = (ctypes.c_uint8 * len(batch))()
-    rc = _lib.load().bgls_verify_multi_hae_sets(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
-                                                _lib.buf(b"".join(k.raw for b in batch for k in pubkeys[b])), key_off, len(batch),
-                                                _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None, None)
-    for i, b in enumerate(batch):
-        out[b] = verdicts[i] == 1 if rc >= 0 else VerifyMultiSignatureWithHAE(curve, aggsigs[b], pubkeys[b], ms[i])
-    return out
+    return settle(len(aggsigs), lambda b: _set_ok(curve, aggsigs[b], pubkeys[b]),
+                  _sets_call("bgls_verify_multi_hae_sets", curve, aggsigs, pubkeys, [[m] for m in msgs], after=(None, None)),
+                  lambda b: VerifyMultiSignatureWithHAE(curve, aggsigs[b], pubkeys[b], bytes(msgs[b])))
 
 
 def KoskVerifyMultiSignatureWithMultiplicity(curve, aggsig, keys, multiplicity, msg):   # bgls/blsKosk.go:137-150
@@ -593,28 +496,18 @@ def KoskVerifyMultiSignatureWithMultiplicity(curve, aggsig, keys, multiplicity, 
         return KoskVerifyMultiSignature(curve, aggsig, keys, msg)
     if len(keys) != len(multiplicity):
         return False
-    if not _g2_keys_ok(curve, keys) or not (isinstance(aggsig, Point) and aggsig.curve is curve and aggsig.group == G1):
+    if not all_points(keys, curve, G2) or not is_point(aggsig, curve, G1):
         return False
-    m2 = b"\x01" + bytes(msg)
+    m2 = _kosk1(msg)
     mult = (ctypes.c_int64 * max(1, len(keys)))(*[int(m) for m in multiplicity])
-    rc = _lib.load().bgls_verify_multi_multiplicity(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), mult,
-                                                    len(keys), _lib.buf(m2), len(m2))
+    rc = _lib.load().bgls_verify_multi_multiplicity(curve.id, _lib.buf(aggsig.raw), cat(keys), mult, len(keys), _lib.buf(m2), len(m2))
     return rc == 1
 
 
 # ---- batch forms of KeyGen / Sign -------------------------------------------------------------
 def LoadPublicKeys(curve, sks):
     """LoadPublicKey (bgls/bgls.go:40-43) for a list of secret keys in one call."""
-    n = len(sks)
-    if n == 0:
-        return []
-    size = len(curve.GetG2().raw)
-    o = _lib.out(n * size)
-    rc = _lib.load().bgls_scale_generator(curve.id, G2, _lib.buf(b"".join(_reduce_scalar(curve, sk if sk >= 0 else sk % curve.GetG1Order()).to_bytes(32, "big") for sk in sks)), n, o)
-    if rc != 0:
-        raise RuntimeError("bgls_scale_generator: %s" % _lib.last_error())
-    raw = bytes(o)
-    return [Point(curve, G2, raw[i * size:(i + 1) * size]) for i in range(n)]
+    return scale_generator(curve, G2, sks)
 
 
 def SignBatch(curve, sks, msgs, kosk=False):
@@ -624,21 +517,12 @@ def SignBatch(curve, sks, msgs, kosk=False):
         return None
     if n == 0:
         return []
-    ms = [(b"\x01" + bytes(m)) if kosk else bytes(m) for m in msgs]
-    off = (ctypes.c_uint64 * (n + 1))()
-    acc = 0
-    for i, m in enumerate(ms):
-        off[i] = acc
-        acc += len(m)
-    off[n] = acc
-    size = len(curve.GetG1().raw)
-    o = _lib.out(n * size)
-    rc = _lib.load().bgls_sign_batch(curve.id, _lib.buf(b"".join(_reduce_scalar(curve, sk if sk >= 0 else sk % curve.GetG1Order()).to_bytes(32, "big") for sk in sks)),
-                                     _lib.buf(b"".join(ms)), off, n, o)
+    o = _lib.out(n * len(curve.GetG1().raw))
+    rc = _lib.load().bgls_sign_batch(curve.id, _lib.buf(b"".join(mag32(curve, sk) for sk in sks)),
+                                     *msgs_arg(_kosk(msgs) if kosk else [bytes(m) for m in msgs]), n, o)
     if rc != 0:
         raise RuntimeError("bgls_sign_batch: %s" % _lib.last_error())
-    raw = bytes(o)
-    return [Point(curve, G1, raw[i * size:(i + 1) * size]) for i in range(n)]
+    return split_points(curve, G1, bytes(o), n)
 
 
 # ---- wrappers that are byte concatenation in front of the same path ---------------------------------------------
@@ -646,40 +530,24 @@ def DistinctMsgSign(curve, sk, msg):                          # bgls/blsDistinct
     return Sign(curve, sk, LoadPublicKey(curve, sk).MarshalUncompressed() + bytes(msg))
 
 
-def _is_point(p, curve, group):
-    return isinstance(p, Point) and p.curve is curve and p.group == group
-
-
 def _verify_single_keyed(curve, sigs, pubkeys, msgs):
     """One bgls_verify_single_distinct_batch (msgs a list) or bgls_check_authentication_batch (msgs None) call for the items made of
     Points of this curve; a nil or foreign point is False, as the single path says.  A call that fails as a whole (an encoding or hashing
-    error somewhere in the batch) is settled item by item through batches of one."""
+    error somewhere in the batch) is settled item by item through batches of one (_marshal.settle)."""
     n = len(sigs)
     if n != len(pubkeys) or (msgs is not None and n != len(msgs)):
         raise ValueError("sigs, pubkeys and msgs differ in length")
-    out = [False] * n
-    batch = [b for b in range(n) if _is_point(sigs[b], curve, G1) and _is_point(pubkeys[b], curve, G2)]
-    if not batch:
-        return out
 
     def call(items):
-        verdicts = (ctypes.c_uint8 * len(items))()
-        sg, ks = _lib.buf(b"".join(sigs[b].raw for b in items)), _lib.buf(b"".join(pubkeys[b].raw for b in items))
+        verdicts = _lib.out(len(items))
+        sg, ks = cat(sigs[b] for b in items), cat(pubkeys[b] for b in items)
         if msgs is None:
             rc = _lib.load().bgls_check_authentication_batch(curve.id, ks, sg, len(items), verdicts, None)
         else:
-            ms = [bytes(msgs[b]) for b in items]
-            rc = _lib.load().bgls_verify_single_distinct_batch(curve.id, sg, ks, _lib.buf(b"".join(ms)), _offsets(ms), len(items), verdicts, None)
+            rc = _lib.load().bgls_verify_single_distinct_batch(curve.id, sg, ks, *msgs_arg([bytes(msgs[b]) for b in items]), len(items), verdicts, None)
         return rc, verdicts
 
-    rc, verdicts = call(batch)
-    for i, b in enumerate(batch):
-        if rc >= 0:
-            out[b] = verdicts[i] == 1
-        elif len(batch) > 1:
-            one_rc, one = call([b])
-            out[b] = one_rc >= 0 and one[0] == 1
-    return out
+    return settle(n, lambda b: is_point(sigs[b], curve, G1) and is_point(pubkeys[b], curve, G2), call)
 
 
 def DistinctMsgVerifySingleSignature(curve, sig, pubkey, msg):   # bgls/blsDistinctMessage.go:37-40
@@ -697,45 +565,28 @@ def DistinctMsgVerifyAggregateSignature(curve, aggsig, keys, msgs):   # bgls/bls
     bytes of a KeySet); there is no duplicate rule."""
     if len(keys) != len(msgs):
         return False
-    if not _is_point(aggsig, curve, G1):
+    if not is_point(aggsig, curve, G1):
         return False
-    ms = [bytes(m) for m in msgs]
+    blob, off = msgs_arg([bytes(m) for m in msgs])
     if isinstance(keys, KeySet):
         if keys.curve is not curve:
             return False
-        return _lib.load().bgls_verify_aggregate_distinct_h(keys.handle, _lib.buf(aggsig.raw), _lib.buf(b"".join(ms)), _offsets(ms), len(ms), None) == 1
-    if not all(_is_point(k, curve, G2) for k in keys):
+        return _lib.load().bgls_verify_aggregate_distinct_h(keys.handle, _lib.buf(aggsig.raw), blob, off, len(msgs), None) == 1
+    if not all_points(keys, curve, G2):
         return False
-    return _lib.load().bgls_verify_aggregate_distinct(curve.id, _lib.buf(aggsig.raw), _lib.buf(b"".join(k.raw for k in keys)), _lib.buf(b"".join(ms)),
-                                                      _offsets(ms), len(ms)) == 1
+    return _lib.load().bgls_verify_aggregate_distinct(curve.id, _lib.buf(aggsig.raw), cat(keys), blob, off, len(msgs)) == 1
 
 
 def DistinctMsgVerifyAggregateSignatures(curve, aggsigs, keys_per_instance, msgs_per_instance):
     """len(aggsigs) independent DistinctMsgVerifyAggregateSignature calls in one batch (bgls_verify_aggregate_distinct_batch): a list of
     bools, one per instance.  An instance that is not made of Points of this curve (mismatched lengths, a foreign point, a KeySet) gets
-    what the single call says about it; a call that fails as a whole is settled instance by instance."""
+    what the single call says about it (_marshal.settle)."""
     if not (len(aggsigs) == len(keys_per_instance) == len(msgs_per_instance)):
         raise ValueError("aggsigs, keys_per_instance and msgs_per_instance differ in length")
-    out = [False] * len(aggsigs)
-    batch = []
-    for b, (sig, keys, msgs) in enumerate(zip(aggsigs, keys_per_instance, msgs_per_instance)):
-        if _is_point(sig, curve, G1) and not isinstance(keys, KeySet) and len(keys) == len(msgs) and all(_is_point(k, curve, G2) for k in keys):
-            batch.append(b)
-        else:
-            out[b] = DistinctMsgVerifyAggregateSignature(curve, sig, keys, msgs)
-    if not batch:
-        return out
-    inst_off = (ctypes.c_uint64 * (len(batch) + 1))()
-    for i, b in enumerate(batch):
-        inst_off[i + 1] = inst_off[i] + len(keys_per_instance[b])
-    msgs = [bytes(m) for b in batch for m in msgs_per_instance[b]]
-    verdicts = (ctypes.c_uint8 * len(batch))()
-    rc = _lib.load().bgls_verify_aggregate_distinct_batch(curve.id, _lib.buf(b"".join(aggsigs[b].raw for b in batch)),
-                                                          _lib.buf(b"".join(k.raw for b in batch for k in keys_per_instance[b])), inst_off, len(batch),
-                                                          _lib.buf(b"".join(msgs)), _offsets(msgs), verdicts, None)
-    for i, b in enumerate(batch):
-        out[b] = verdicts[i] == 1 if rc >= 0 else DistinctMsgVerifyAggregateSignature(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b])
-    return out
+    return settle(len(aggsigs),
+                  lambda b: _set_ok(curve, aggsigs[b], keys_per_instance[b]) and len(keys_per_instance[b]) == len(msgs_per_instance[b]),
+                  _sets_call("bgls_verify_aggregate_distinct_batch", curve, aggsigs, keys_per_instance, msgs_per_instance),
+                  lambda b: DistinctMsgVerifyAggregateSignature(curve, aggsigs[b], keys_per_instance[b], msgs_per_instance[b]))
 
 
 def Authenticate(curve, sk):                                  # bgls/blsKosk.go:44-55: a signature on the marshalled key
@@ -807,34 +658,27 @@ def AmsVerifySignature(curve, apk, signers, aggKey, aggSig, msg):   # blsAsmSigs
 def AmsVerifySignatures(curve, apks, signers, aggKeys, aggSigs, msgs):
     """len(apks) independent AmsVerifySignature calls (blsAsmSigs.go:48-59) in one bgls_ams_verify_batch call: a list of bools, one per
     item.  An item that is not made of Points of this curve (a nil or foreign signature or key) or has a signer index outside
-    [0, 2^32) gets what AmsVerifySignature says about it alone; an empty signer list gives False (the reference panics); a call that
-    fails as a whole is settled item by item."""
+    [0, 2^32) gets what AmsVerifySignature says about it alone; an empty signer list gives False (the reference panics) (_marshal.settle)."""
     n = len(apks)
     if not (n == len(signers) == len(aggKeys) == len(aggSigs) == len(msgs)):
         raise ValueError("apks, signers, aggKeys, aggSigs and msgs differ in length")
-    out = [False] * n
-    batch = []
-    for b in range(n):
-        if not (isinstance(aggSigs[b], Point) and aggSigs[b].curve is curve and aggSigs[b].group == G1
-                and _g2_keys_ok(curve, [apks[b], aggKeys[b]])
-                and all(isinstance(i, int) and 0 <= i < 1 << 32 for i in signers[b])):
-            out[b] = AmsVerifySignature(curve, apks[b], signers[b], aggKeys[b], aggSigs[b], bytes(msgs[b]))
-        elif len(signers[b]):
-            batch.append(b)
-    if not batch:
-        return out
-    flat = [i for b in batch for i in signers[b]]
-    soff = (ctypes.c_uint64 * (len(batch) + 1))()
-    for i, b in enumerate(batch):
-        soff[i + 1] = soff[i] + len(signers[b])
-    ms = [bytes(msgs[b]) for b in batch]
-    verdicts = (ctypes.c_uint8 * len(batch))()
-    rc = _lib.load().bgls_ams_verify_batch(curve.id, _lib.buf(b"".join(apks[b].raw for b in batch)), _lib.buf(b"".join(aggKeys[b].raw for b in batch)),
-                                           _lib.buf(b"".join(aggSigs[b].raw for b in batch)), (ctypes.c_uint32 * len(flat))(*flat), soff, len(batch),
-                                           _lib.buf(b"".join(ms)), _offsets(ms), verdicts, None)
-    for i, b in enumerate(batch):
-        out[b] = verdicts[i] == 1 if rc >= 0 else AmsVerifySignature(curve, apks[b], signers[b], aggKeys[b], aggSigs[b], ms[i])
-    return out
+
+    def sendable(b):
+        return (is_point(aggSigs[b], curve, G1) and all_points([apks[b], aggKeys[b]], curve, G2)
+                and all(isinstance(i, int) and 0 <= i < 1 << 32 for i in signers[b]))
+
+    def call(items):
+        flat = [i for b in items for i in signers[b]]
+        verdicts = _lib.out(len(items))
+        rc = _lib.load().bgls_ams_verify_batch(curve.id, cat(apks[b] for b in items), cat(aggKeys[b] for b in items), cat(aggSigs[b] for b in items),
+                                               (ctypes.c_uint32 * len(flat))(*flat), prefix_u64(len(signers[b]) for b in items), len(items),
+                                               *msgs_arg([bytes(msgs[b]) for b in items]), verdicts, None)
+        return rc, verdicts
+
+    def single(b):                                   # a sendable item that was not sent has no signers
+        return False if sendable(b) and len(signers[b]) == 0 else AmsVerifySignature(curve, apks[b], signers[b], aggKeys[b], aggSigs[b], bytes(msgs[b]))
+
+    return settle(n, lambda b: sendable(b) and len(signers[b]) > 0, call, single)
 
 
 def AmsVerifySignatureWithSetCheck(curve, check, apk, signers, aggKey, aggSig, msg):   # blsAsmSigs.go:61-66

@@ -7,18 +7,11 @@ curves/curve_test.go and bgls/bgls_test.go.
 
 All arithmetic happens on the GPU.  Nothing here computes field or group operations.
 """
-import ctypes
 from . import _lib
+from ._marshal import all_points, cat, is_point, mag32, msgs_arg, split_points
 
 ALTBN128, BLS12_381 = 0, 1
 G1, G2 = 1, 2
-
-
-def _reduce_scalar(curve, mag):
-    """The ABI takes 32-byte magnitudes.  The reference multiplies by the exact big.Int; on points of order r (every
-    validated Point, every GT element) a magnitude of 2^256 or more acts as its residue modulo the group order, so larger
-    factors are reduced modulo GetG1Order() -- in every path, never modulo 2^256."""
-    return mag if mag < 1 << 256 else mag % curve.GetG1Order()
 
 
 class Point:
@@ -60,11 +53,9 @@ class Point:
     def Mul(self, scalar):
         """Point.Mul (altbn128.go:107-121,235-249; bls12_381.go:65-76,126-137): negative scalars
         negate then multiply, zero gives infinity.  The caller's scalar is NOT mutated."""
-        sign = 1 if scalar < 0 else 0
-        mag = _reduce_scalar(self.curve, -scalar if scalar < 0 else scalar)
         o = _lib.out(len(self.raw))
-        rc = _lib.load().bgls_scale_points(self.curve.id, self.group, _lib.buf(self.raw), _lib.buf(mag.to_bytes(32, "big")),
-                                           _lib.buf(bytes([sign])), 1, o)
+        rc = _lib.load().bgls_scale_points(self.curve.id, self.group, _lib.buf(self.raw), _lib.buf(mag32(self.curve, abs(scalar))),
+                                           _lib.buf(bytes([1 if scalar < 0 else 0])), 1, o)
         if rc != 0:
             raise RuntimeError("bgls_scale_points: %d %s" % (rc, _lib.last_error()))
         return Point(self.curve, self.group, bytes(o))
@@ -103,10 +94,8 @@ class PointT:
 
     def Mul(self, scalar):
         """PointT.Mul (curves/altbn128.go:273-281, curves/bls12_381.go:170-173): exponentiation in GT."""
-        sign = 1 if scalar < 0 else 0
-        mag = _reduce_scalar(self.curve, -scalar if scalar < 0 else scalar)
         o = _lib.out(len(self.raw))
-        rc = _lib.load().bgls_gt_pow(self.curve.id, _lib.buf(self.raw), _lib.buf(mag.to_bytes(32, "big")), sign, o)
+        rc = _lib.load().bgls_gt_pow(self.curve.id, _lib.buf(self.raw), _lib.buf(mag32(self.curve, abs(scalar))), 1 if scalar < 0 else 0, o)
         if rc != 0:
             return None
         return PointT(self.curve, bytes(o))
@@ -210,20 +199,11 @@ class CurveSystem:
 
     def HashToG1Batch(self, messages):
         n = len(messages)
-        blob = b"".join(bytes(m) for m in messages)
-        off = (ctypes.c_uint64 * (n + 1))()
-        acc = 0
-        for i, m in enumerate(messages):
-            off[i] = acc
-            acc += len(m)
-        off[n] = acc
         o = _lib.out(n * self._pt_size(G1))
-        rc = _lib.load().bgls_hash_to_g1(self.id, _lib.buf(blob), off, n, o)
+        rc = _lib.load().bgls_hash_to_g1(self.id, *msgs_arg([bytes(m) for m in messages]), n, o)
         if rc != 0:
             raise RuntimeError("bgls_hash_to_g1: %d %s" % (rc, _lib.last_error()))
-        s = self._pt_size(G1)
-        raw = bytes(o)
-        return [Point(self, G1, raw[i * s:(i + 1) * s]) for i in range(n)]
+        return split_points(self, G1, bytes(o), n)
 
     def HashToG1Keyed(self, keys, msgs=None):
         """HashToG1 of inputs derived from G2 keys, built on the device (bgls_hash_to_g1_keyed): key i's uncompressed bytes followed by
@@ -231,64 +211,43 @@ class CurveSystem:
         n = len(keys)
         if msgs is not None and len(msgs) != n:
             raise ValueError("keys and msgs differ in length")
-        if any(not (isinstance(k, Point) and k.curve is self and k.group == G2) for k in keys):
+        if not all_points(keys, self, G2):
             raise ValueError("HashToG1Keyed takes G2 Points of this curve")
-        blob, off = None, None
-        if msgs is not None:
-            ms = [bytes(m) for m in msgs]
-            blob = _lib.buf(b"".join(ms))
-            off = (ctypes.c_uint64 * (n + 1))()
-            for i, m in enumerate(ms):
-                off[i + 1] = off[i] + len(m)
-        s = self._pt_size(G1)
-        o = _lib.out(n * s)
-        rc = _lib.load().bgls_hash_to_g1_keyed(self.id, 0 if msgs is not None else 1, _lib.buf(b"".join(k.raw for k in keys)), blob, off, n, o)
+        blob, off = (None, None) if msgs is None else msgs_arg([bytes(m) for m in msgs])
+        o = _lib.out(n * self._pt_size(G1))
+        rc = _lib.load().bgls_hash_to_g1_keyed(self.id, 0 if msgs is not None else 1, cat(keys), blob, off, n, o)
         if rc != 0:
             raise RuntimeError("bgls_hash_to_g1_keyed: %d %s" % (rc, _lib.last_error()))
-        raw = bytes(o)
-        return [Point(self, G1, raw[i * s:(i + 1) * s]) for i in range(n)]
+        return split_points(self, G1, bytes(o), n)
 
     def Pair(self, p1, p2):
         return self.PairingProduct([p1], [p2])
 
     def PairBatch(self, pts1, pts2):
         """len(pts1) independent Pair calls in one bgls_pair_batch call: a list with Pair's PointT per item, None where Pair itself
-        answers (nil, false).  An item that is not a G1 / G2 Point of this curve, or a call that fails as a whole (an encoding error
-        somewhere in the batch), is settled item by item with Pair."""
+        answers (nil, false).  The batch-and-settle rule of _marshal.settle, written out here because the answers are GT elements, not
+        verdict bytes: the batch call comes first, and then every item that is not a G1 / G2 Point of this curve, or every item of a call
+        that failed as a whole (any rc but 0), gets Pair's answer, in index order."""
         if len(pts1) != len(pts2):
             raise ValueError("pts1 and pts2 differ in length")
-        n = len(pts1)
-        if n == 0:
-            return []
         gtb = 12 * self.fp_bytes
-        out = [None] * n
-        batch = [i for i, (a, b) in enumerate(zip(pts1, pts2))
-                 if isinstance(a, Point) and isinstance(b, Point) and a.curve is self and b.curve is self and a.group == G1 and b.group == G2]
+        out = {}
+        batch = [i for i in range(len(pts1)) if is_point(pts1[i], self, G1) and is_point(pts2[i], self, G2)]
         if batch:
             o = _lib.out(len(batch) * gtb)
-            rc = _lib.load().bgls_pair_batch(self.id, _lib.buf(b"".join(pts1[i].raw for i in batch)), _lib.buf(b"".join(pts2[i].raw for i in batch)),
-                                             len(batch), o)
-            if rc == 0:
+            if _lib.load().bgls_pair_batch(self.id, cat(pts1[i] for i in batch), cat(pts2[i] for i in batch), len(batch), o) == 0:
                 raw = bytes(o)
-                for k, i in enumerate(batch):
-                    out[i] = PointT(self, raw[k * gtb:(k + 1) * gtb])
-            else:
-                batch = []
-        for i in set(range(n)) - set(batch):
-            out[i] = self.Pair(pts1[i], pts2[i])[0]
-        return out
+                out = {i: PointT(self, raw[k * gtb:(k + 1) * gtb]) for k, i in enumerate(batch)}
+        return [out[i] if i in out else self.Pair(pts1[i], pts2[i])[0] for i in range(len(pts1))]
 
     def PairingProduct(self, pts1, pts2):
         """One C call for the whole slice (replaces concurrentPairingProduct, curve.go:125-170)."""
         if len(pts1) != len(pts2):
             return None, False
-        for a, b in zip(pts1, pts2):
-            if not (isinstance(a, Point) and isinstance(b, Point) and a.curve is self and b.curve is self
-                    and a.group == G1 and b.group == G2):
-                return None, False
+        if not (all_points(pts1, self, G1) and all_points(pts2, self, G2)):
+            return None, False
         o = _lib.out(12 * self.fp_bytes)
-        rc = _lib.load().bgls_pairing_product(self.id, _lib.buf(b"".join(p.raw for p in pts1)),
-                                              _lib.buf(b"".join(p.raw for p in pts2)), len(pts1), o)
+        rc = _lib.load().bgls_pairing_product(self.id, cat(pts1), cat(pts2), len(pts1), o)
         if rc != 0:
             return None, False
         return PointT(self, bytes(o)), True
@@ -308,7 +267,7 @@ def AggregatePoints(points):
         raise ValueError("AggregatePoints of an empty slice (the reference never returns here, curve.go:94-108)")
     c, g = points[0].curve, points[0].group
     o = _lib.out(len(points[0].raw))
-    rc = _lib.load().bgls_aggregate_points(c.id, g, _lib.buf(b"".join(p.raw for p in points)), len(points), o)
+    rc = _lib.load().bgls_aggregate_points(c.id, g, cat(points), len(points), o)
     if rc != 0:
         raise RuntimeError("bgls_aggregate_points: %d %s" % (rc, _lib.last_error()))
     return Point(c, g, bytes(o))
@@ -324,11 +283,9 @@ def ScalePoints(pts, factors):
         return []
     c, g = pts[0].curve, pts[0].group
     signs = bytes(2 if f is None else (1 if f < 0 else 0) for f in factors)
-    mags = b"".join((0 if f is None else _reduce_scalar(c, abs(f))).to_bytes(32, "big") for f in factors)
-    s = len(pts[0].raw)
-    o = _lib.out(len(pts) * s)
-    rc = _lib.load().bgls_scale_points(c.id, g, _lib.buf(b"".join(p.raw for p in pts)), _lib.buf(mags), _lib.buf(signs), len(pts), o)
+    mags = b"".join(mag32(c, 0 if f is None else abs(f)) for f in factors)
+    o = _lib.out(len(pts) * len(pts[0].raw))
+    rc = _lib.load().bgls_scale_points(c.id, g, cat(pts), _lib.buf(mags), _lib.buf(signs), len(pts), o)
     if rc != 0:
         raise RuntimeError("bgls_scale_points: %d %s" % (rc, _lib.last_error()))
-    raw = bytes(o)
-    return [Point(c, g, raw[i * s:(i + 1) * s]) for i in range(len(pts))]
+    return split_points(c, g, bytes(o), len(pts))
